@@ -15,6 +15,12 @@ one kernel launch) -- over one batch of synthetic 22.05 kHz clips already reside
 Plans/tables are created outside the timed region.  The timed region is EXACTLY --steps steps bracketed by a
 barrier + device synchronize on both sides; the max over ranks is reported.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs DIR if given, and the line
+(contract keys, `config`, `roofline` of the timed kernel from the timed steps' own events).  Everything else below -- the repeats,
+the side measurements, `gathered` at N > 1, `cpu_baseline` and `parity` -- runs only with --full:
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+
 Output (rank 0): ONE short JSON line on stdout -- the contract's keys, `roofline` (timed kernel) with the path's other fractions folded in as SCALARS of `roofline`
 (stft_frac / istft_frac / stream_forward_frac / stream_inverse_frac / cqt_lite_frac, stft_v2_frac / stft_v3_frac / mel_pc_ms of `kernel_forms`, + the best / worst of `--placements` allocations of the 2.7 GB spectrum: its
 placement moves the store-bound transform 0.63-0.75 ms, profiles/r05_pitch.md), `cpu_baseline`, `parity`, `scaling_base` (N = 1 at 512 clips per GPU), one number per
@@ -241,6 +247,21 @@ def self_launch(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
+DUMP_CLIPS = 64  # 64 x 128 x 1292 float32 = 42 MB over all ranks
+DUMP_SEED = 2048
+
+
+def dump_outputs(out_dir, M, rank, world):
+    """--dump-outputs: the mel spectrograms the last timed step wrote, for a fixed, seeded sample of this rank's clips (the same clips from
+    run to run with the same arguments) -> out_dir/melspectrogram.npy (N = 1) or melspectrogram_rank<r>.npy, float32 (clips, n_mels, frames)."""
+    batch = M.shape[0]
+    k = min(batch, max(1, DUMP_CLIPS // world))
+    clips = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(batch, size=k, replace=False))
+    sample = M[clips.tolist()].cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "melspectrogram.npy" if world == 1 else f"melspectrogram_rank{rank}.npy"), sample)
+
+
 def dry_run(args, torch, world, rank):
     """--dry-run: everything around the step (see the flag's help).  No kernel, no library, no GPU; never a measurement."""
     import torch.distributed as dist
@@ -328,7 +349,8 @@ def compact_line(line):
         out["scaling_base"] = {k: r(v) for k, v in line["scaling_base"].items()} if isinstance(line["scaling_base"], dict) else line["scaling_base"]
     if "gathered" in line and isinstance(line["gathered"], dict):
         out["gathered"] = {k: r(line["gathered"].get(k)) for k in ("value", "unit", "ms_per_step", "chunks", "bytes_per_rank", "backend", "own_rows_match", "full_matches_unsharded", "error") if k in line["gathered"]}
-    out["repeats"] = {"ms_per_step_min": r(get(line, "repeats", "ms_per_step_min")), "ms_per_step_median": r(get(line, "repeats", "ms_per_step_median"))}
+    if "repeats" in line:
+        out["repeats"] = {"ms_per_step_min": r(get(line, "repeats", "ms_per_step_min")), "ms_per_step_median": r(get(line, "repeats", "ms_per_step_median"))}
     side = {"dropin_torch_ms": get(line, "dropin_torch", "ms_per_call"), "numpy_mel_ms_64clips": get(line, "end_to_end_numpy", "melspectrogram", "ms"),
             "numpy_stft_ms_64clips": get(line, "end_to_end_numpy", "stft", "ms"), "power_to_db_ms": get(line, "power_to_db", "ms_per_call"), "mfcc_ms": get(line, "mfcc", "ms_per_call"),
             "griffinlim_ms_per_iter_32clips": get(line, "griffinlim", "ms_per_iteration"), "griffinlim_ms_setup": get(line, "griffinlim", "ms_setup"),
@@ -367,6 +389,10 @@ def main():
                                                             "the JSON line with the step replaced by a 1 ms host sleep; `value` is null and `data` says so")
     ap.add_argument("--variant", type=int, default=None)
     ap.add_argument("--iters", type=int, default=None)
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline figure: the repeats of the timed region, the side measurements, "
+                                                        "the N > 1 `gathered` step and the CPU baseline with its parity check (the --no-* flags above thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32): the mel "
+                                                                        "spectrograms of a fixed, seeded sample of at most 64 clips (split over the ranks)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -462,15 +488,18 @@ def main():
         tw = torch.tensor([wall], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, M, rank, world)
     # five more repeats of the same region (no collectives): run-to-run spread
-    rep = [timed(step_mel, args.steps, 0, collective=False)[1] / args.steps * 1e3 for _ in range(5)]
+    rep = [timed(step_mel, args.steps, 0, collective=False)[1] / args.steps * 1e3 for _ in range(5)] if args.full else None
 
     side = {}
     only = set(filter(None, os.environ.get("LRA_BENCH_ONLY", "").split(",")))  # debugging aid: run only these side measurements
+    no_side = args.no_side or not args.full
 
     def measure(name, fn):
         """A side measurement never breaks the contract line."""
-        if args.no_side or (only and name not in only):
+        if no_side or (only and name not in only):
             return
         try:
             side[name] = fn()
@@ -478,7 +507,7 @@ def main():
             side[name] = {"error": repr(exc)}
 
     # ---- N > 1: the same step with every rank ending up with the full result (chunked gather behind the compute) --------------
-    if world > 1 and not args.no_side:
+    if world > 1 and not no_side:
         pieces = chunk_ranges(batch, args.gather_chunks)
 
         def step_gathered():
@@ -513,7 +542,7 @@ def main():
 
     # ---- single-GPU side measurements (their timing helpers contain no collectives) -------------------------------------------
     snr_db = None
-    if world == 1 and not args.no_side:
+    if world == 1 and not no_side:
         # The complex spectrum is 2.7 GB, and WHERE that allocation lands moves the store-bound transform between 0.63 and 0.75 ms inside one process
         # (profiles/r05_pitch.md): one allocation is a draw.  Several are made, the transform is timed on each, and everything below runs on the
         # MEDIAN one; best / worst are reported beside it (`placement`).
@@ -1042,8 +1071,9 @@ def main():
                          "limited_by": "valu/lds issue, not HBM (achieved / peak / frac here ARE the HBM figures BASELINE's metric asks for; `valu_frac` = the same launch against the f32 vector peak, "
                                        "which is the side of the ridge this kernel sits on)",
                          "note": "this kernel sits on the LDS / VALU side of the ridge (~65 kFLOP and ~500 LDS cycles per 2 560 B); see roofline_stft for the HBM-bound kernel"},
-            "repeats": {"ms_per_step_min": min(rep), "ms_per_step_median": statistics.median(rep), "ms_per_step_all": rep, "what": "5 more repeats of the timed region (HIP events, no collectives)"},
         }
+        if rep:
+            line["repeats"] = {"ms_per_step_min": min(rep), "ms_per_step_median": statistics.median(rep), "ms_per_step_all": rep, "what": "5 more repeats of the timed region (HIP events, no collectives)"}
         # the fused mel kernel against the f32 vector peak (~65 kFLOP per frame by the 5 N log2 N convention)
         line["roofline_valu"] = {"bound": "valu", "kernel": line["roofline"]["kernel"], "achieved": frames_per_step * 65e3 / launch_s / 1e12, "peak": 157.3, "unit": "TFLOP/s",
                                  "frac": frames_per_step * 65e3 / launch_s / 1e12 / 157.3, "flop_per_frame": 65e3}
@@ -1075,7 +1105,7 @@ def main():
                         line[key]["traffic_box"] = "profile"  # measured under rocprofv3 on the builder's box, not on the box this line was timed on
         except Exception:
             pass
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 clip = (y[0].cpu().numpy(), M[0].cpu().numpy())
             except Exception:

@@ -3,6 +3,7 @@
 TEST INFRASTRUCTURE ONLY; runs only where ``/root/reference`` exists (the build container):
 
     python oracle/make_golden.py
+    python oracle/make_golden.py reference_calls   # tests/golden/reference_calls.npz (golden_cases.ReferenceCalls)
 
 Each fixture stores the input PCM, the call parameters (JSON) and the reference outputs
 (``librosa.stft``, ``librosa.feature.melspectrogram``, ``librosa.istft``).  The fixtures travel to
@@ -225,7 +226,21 @@ def make_db_mfcc(librosa, meta):
     print("db_mfcc done")
 
 
+def make_reference_calls():
+    """The tests of tests/test_oracle.py that compare the oracle with the reference on seeded draws, run once against the unmodified
+    reference with their outputs recorded (golden_cases.ReferenceCalls, LRA_RECORD_REFERENCE=1)."""
+    import subprocess
+
+    if os.path.exists(golden_cases.REFERENCE_CALLS):
+        os.remove(golden_cases.REFERENCE_CALLS)
+    test = os.path.join(os.path.dirname(HERE), "tests", "test_oracle.py")
+    return subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", test, "-k", "live_reference or normalize_matches"],
+                           env=dict(os.environ, LRA_RECORD_REFERENCE="1"))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "reference_calls":
+        sys.exit(make_reference_calls())
     if len(sys.argv) > 1 and sys.argv[1] in ("griffinlim", "vocoder", "pcen", "cqt", "hpss", "resample"):  # only this fixture (the others are unchanged)
         _librosa = ref_shim.load_reference()
         import scipy as _scipy

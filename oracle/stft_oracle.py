@@ -15,7 +15,8 @@ The restatement is pinned three ways (see ``tests/test_oracle.py``):
 2. against outputs of the reference itself, generated in the build container by importing the
    unmodified reference through ``oracle/ref_shim.py`` and committed as fixtures under
    ``tests/golden/`` (script: ``oracle/make_golden.py``);
-3. when ``/root/reference`` is present, live against the reference on seeded random cases.
+3. against the reference on seeded random cases, its outputs recorded once into
+   ``tests/golden/reference_calls.npz`` (``golden_cases.ReferenceCalls``; ``make_golden.py reference_calls``).
 
 Third-party arithmetic on the path that is NOT under ``/root/reference`` and is used here
 through the very same library the reference calls: ``scipy.fft.rfft/irfft`` (pocketfft, scipy

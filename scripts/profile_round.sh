@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $R/bench.py --no-cpu-baseline --no-cqt --no-power --no-scaling-base --placements 1"
+BENCH="python $R/bench.py --full --no-cpu-baseline --no-cqt --no-power --no-scaling-base --placements 1"
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o r -- $BENCH --steps 20 --warmup 5 > "$OUT/stats.log" 2>&1
 # (round 5: on one box every pass died with a GPU memory fault right after HSA initialisation and then sat out its timeout -- 20 GPU-minutes; stop at the first such pass)
 if grep -q "Memory access fault" "$OUT/stats.log" || [ ! -d "$OUT/stats" ]; then echo "profile_round: the stats pass failed on this box, giving up"; tail -5 "$OUT/stats.log"; exit 1; fi

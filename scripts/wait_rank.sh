@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export TMPDIR=/tmp; cd /tmp
 O=$R/gpurun_out/wait_rank; mkdir -p $O
-timeout 900 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS -d $O/a -o r -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-power --no-scaling-base --placements 1 --prewarm-ms 50 > $O/a.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS -d $O/a -o r -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-power --no-scaling-base --placements 1 --prewarm-ms 50 > $O/a.log 2>&1
 python - <<PY
 import csv, collections, glob
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()

@@ -27,6 +27,12 @@ def test_library_exports_every_declared_symbol():
     from librosa_amd import _native
 
     assert os.path.exists(_native.LIB_PATH), "build the library first: python -c 'import __graft_entry__ as g; g.build()'"
+    # the load order of _native.load_library: torch's HIP runtime first, so that the library binds to it.  Loaded the other way round,
+    # the process holds two HIP runtimes and torch finds no device in every later test of the same session.
+    try:
+        import torch  # noqa: F401
+    except Exception:
+        pass
     lib = ctypes.CDLL(_native.LIB_PATH)
     missing = [n for n in _declared_symbols() if not hasattr(lib, n)]
     assert not missing, f"declared in the header but not exported: {missing}"
