@@ -1035,21 +1035,22 @@ template <class Cfg, class RG> LRA_HD int melr_tile_slot(const StftArgs<typename
     if ((a.n_frames & 3) == 0 && Cfg::TF >= 64) return (int)(((long long)clip * a.n_mels * a.n_frames + (long long)b * a.n_frames + frame) & (MT - 1));
     return (int)((row0 + frame) & (MT - 1));
 }
-// stores slots max(0, s8 - it) .. s8 of band slot b's tile (the frames this slot has produced so far); a whole tile leaves as two 16-byte stores
-template <class Cfg, class RG> LRA_HD void melr_burst(const StftArgs<typename Cfg::real>& a, long long row0, int frame, int s8, int it, int b, RG& rg) {
-    using T = typename Cfg::real;
-    constexpr int MT = RG::MELR_TILE;
-    T* __restrict__ row = a.Mel + (row0 + frame - s8);
+// stores slots max(0, s8 - it) .. s8 of a tile to row[0 ..) (row: the element of tile slot 0); a whole tile leaves as two 16-byte stores
+template <class T, int MT> LRA_HD void melr_burst_row(T* __restrict__ row, int s8, int it, const T (&mt)[MT]) {
     if constexpr (sizeof(T) == 4 && (MT == 8 || MT == 4)) {
         if (LRA_MEL_BURST16 && s8 == MT - 1 && it >= MT - 1) {
-            store4_unaligned(row, rg.mt[b][0], rg.mt[b][1], rg.mt[b][2], rg.mt[b][3]);
-            if constexpr (MT == 8) store4_unaligned(row + 4, rg.mt[b][4], rg.mt[b][5], rg.mt[b][6], rg.mt[b][7]);
+            store4_unaligned(row, mt[0], mt[1], mt[2], mt[3]);
+            if constexpr (MT == 8) store4_unaligned(row + 4, mt[4], mt[5], mt[6], mt[7]);
             return;
         }
     }
     LRA_UNROLL
     for (int k = 0; k < MT; ++k)
-        if (k <= s8 && k >= s8 - it) row[k] = rg.mt[b][k];
+        if (k <= s8 && k >= s8 - it) row[k] = mt[k];
+}
+// stores slots max(0, s8 - it) .. s8 of band slot b's tile (the frames this slot has produced so far)
+template <class Cfg, class RG> LRA_HD void melr_burst(const StftArgs<typename Cfg::real>& a, long long row0, int frame, int s8, int it, int b, RG& rg) {
+    melr_burst_row(a.Mel + (row0 + frame - s8), s8, it, rg.mt[b]);
 }
 
 // phase: mel[m] = sum of the B totals of segment m's pieces + sum of the A totals of segment m+1's pieces

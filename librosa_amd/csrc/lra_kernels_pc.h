@@ -76,6 +76,19 @@ template <class Cfg> LRA_HD bool pc_fits_budget(int hd, int power_mode) {
     return hd == 4 && (power_mode == POW_TWO || Cfg::PLAN == 1);
 }
 
+// one producer's tile of two bands x eight frames.  On the device a 16-wide register vector: an element picked by a wave-uniform index is
+// written by one indexed register move (s_set_gpr_idx_on, v_mov_b32, s_set_gpr_idx_off); eight compares and eight selects per band
+// otherwise, the form a per-lane slot still needs (pc_combine<.., false>).
+#ifdef LRA_HOSTSIM
+struct PcTileV {
+    float e[16];
+    float& operator[](int i) { return e[i]; }
+    float operator[](int i) const { return e[i]; }
+};
+#else
+typedef float PcTileV __attribute__((ext_vector_type(16)));
+#endif
+
 // consumer state
 template <class Cfg> struct PcRegs {
     using T = typename Cfg::real;
@@ -86,13 +99,38 @@ template <class Cfg> struct PcRegs {
     T keep[Cfg::R];     // 0 where a running sum restarts
     T pw[Cfg::R], pw_extra;
     int mad[NB][2 * PH];       // byte addresses (workgroup LDS) of the piece totals of bands 2 tf and 2 tf + 1: B list, then A list
-    T mt[NP][NB][TILE];        // per producer: the last eight frames of the two bands
+    int pwa[4], pwx;           // byte offsets in a power row of this thread's runs (lo / hi half of run 0, then of run 1) and of bin M (thread 0; 0 elsewhere)
+    T* row[NB];                // output row of bands 2 tf, 2 tf + 1 (element 0 of the clip's row; valid bands only)
+    int ph[NP][NB];            // tile slot of producer s's first frame in band slot b (pc_tile_uniform; the slot of frame `it` is ph + it mod TILE)
+    PcTileV mt[NP];            // per producer: the last eight frames of the two bands (element TILE b + slot)
 };
-// what melr_tile_slot / melr_burst (lra_kernels.h) need of a register struct: one producer's tile
-template <class Cfg> struct PcTile {
-    static constexpr int MELR_TILE = PcRegs<Cfg>::TILE;
-    typename Cfg::real (&mt)[PcRegs<Cfg>::NB][PcRegs<Cfg>::TILE];
-};
+// The tile slot is tied to the absolute element index in the output (melr_tile_slot).  Where rows start 0 or 16 bytes into a 32-byte piece
+// (n_frames a multiple of 4; bands 2 tf, 2 tf + 1 have the same parity for every lane) it is one value per wave, producer slot and band
+// slot: the consumer then keeps it in a scalar register, picks the tile register by a scalar branch and takes the burst branch on a scalar
+// condition.  Otherwise every lane has its own slot (a select per tile register).  One branch per launch picks the form.
+template <class Cfg> LRA_HD bool pc_tile_uniform(const StftArgs<typename Cfg::real>& a) { return !LRA_MEL_ALIGNED_BURSTS || ((a.n_frames & 3) == 0 && Cfg::TF >= 64); }
+// piece-total pair at a hoisted address (rg.mad).  On the device the address is the absolute 32-bit LDS address, taken out of the compiler's
+// sight once in the prologue: as a symbol-relative offset the base add was sunk next to each of the sixteen reads, inside the frame loop.
+#ifdef LRA_HOSTSIM
+LRA_HD int pc_mad_addr(Lds wg, int ad) { return ad; }
+LRA_HD cx<float> pc_pair_ld(Lds wg, int addr) { return lds_ld<cx<float>>(wg, addr); }
+#else
+__device__ __forceinline__ int pc_mad_addr(Lds wg, int ad) {
+    int addr = (int)(unsigned int)(size_t)(__attribute__((address_space(3))) char*)(wg.base + ad);
+    asm volatile("" : "+v"(addr));
+    return addr;
+}
+__device__ __forceinline__ cx<float> pc_pair_ld(Lds, int addr) {
+    typedef float f2v __attribute__((ext_vector_type(2)));
+    const f2v t = *(const volatile __attribute__((address_space(3))) f2v*)(size_t)(unsigned int)addr;
+    return __builtin_bit_cast(cx<float>, t);
+}
+#endif
+// band slot b's part of a tile as an array, for melr_burst_row
+template <class T, int MT> LRA_HD void pc_tile_band(const PcTileV& t, int b, T (&out)[MT]) {
+    LRA_UNROLL
+    for (int k = 0; k < MT; ++k) out[k] = t[MT * b + k];
+}
 
 // ---- flags ---------------------------------------------------------------------------------------------------------------------
 #ifdef LRA_HOSTSIM
@@ -123,6 +161,11 @@ __device__ __forceinline__ void pc_wait(Lds l, int off, int want, unsigned int* 
         __builtin_amdgcn_s_sleep(2);
     }
     pc_fence();
+}
+// as pc_wait, for a flag that is nearly always set already: one read and a scalar branch, the bounded sleeping loop only behind it
+__device__ __forceinline__ void pc_wait_ready(Lds l, int off, int want, unsigned int* sticky) {
+    if (LRA_UNLIKELY(LRA_UNIFORM(pc_flag_load(l, off)) < want)) pc_wait(l, off, want, sticky);
+    else pc_fence();
 }
 #endif
 
@@ -172,7 +215,8 @@ template <class Cfg, int HD, int PM> LRA_HD void pc_last_power_row(const StftArg
 }
 
 // ---- consumer --------------------------------------------------------------------------------------------------------------------
-template <class Cfg> LRA_HD void pc_consumer_prologue(const StftArgs<typename Cfg::real>& a, int tf, PcRegs<Cfg>& rg) {
+// (clip, f_first, iters: the workgroup's clip, first frame and frames per producer slot -- the output rows and tile phases depend on them)
+template <class Cfg> LRA_HD void pc_consumer_prologue(const StftArgs<typename Cfg::real>& a, int clip, int f_first, int iters, int tf, PcRegs<Cfg>& rg, Lds wg) {
     using T = typename Cfg::real;
     using C = typename Cfg::cplx;
     using RG = PcRegs<Cfg>;
@@ -194,33 +238,46 @@ template <class Cfg> LRA_HD void pc_consumer_prologue(const StftArgs<typename Cf
             LRA_UNROLL
             for (int q = 0; q < RG::PH; ++q) {
                 const int ad = PcLayout<Cfg>::rs_off() + (m < a.n_mels ? a.melr_addr[(h * a.melr_pmax + q) * a.n_mels + m] : a.melr_zero);
-                rg.mad[b][h * RG::PH + q] = ad & ~(2 * (int)sizeof(T) - 1);  // (the B list addresses the B half of a pair; whole pairs are read)
+                rg.mad[b][h * RG::PH + q] = pc_mad_addr(wg, ad & ~(2 * (int)sizeof(T) - 1));  // (the B list addresses the B half of a pair; whole pairs are read)
             }
         }
+    }
+    LRA_UNROLL
+    for (int run = 0; run < 2; ++run) {
+        const int first = 8 * (run * TF + tf);
+        rg.pwa[2 * run] = v2_pw_index<Cfg>(first) * (int)sizeof(T);
+        rg.pwa[2 * run + 1] = v2_pw_index<Cfg>(first + 4) * (int)sizeof(T);
+    }
+    rg.pwx = (tf == 0 ? v2_pw_index<Cfg>(Cfg::M) : 0) * (int)sizeof(T);
+    LRA_UNROLL
+    for (int b = 0; b < RG::NB; ++b) {
+        const int m = RG::NB * tf + b;
+        rg.row[b] = a.Mel + ((long long)clip * a.n_mels + (m < a.n_mels ? m : 0)) * a.n_frames;
     }
     LRA_UNROLL
     for (int s = 0; s < RG::NP; ++s) {
         LRA_UNROLL
         for (int b = 0; b < RG::NB; ++b) {
+            // (as melr_tile_slot's scalar form at frame f_first + s iters; used only where pc_tile_uniform holds)
+            rg.ph[s][b] = LRA_MEL_ALIGNED_BURSTS ? (int)(((long long)clip * a.n_mels * a.n_frames + (long long)b * a.n_frames + f_first + s * iters) & (RG::TILE - 1)) : 0;
             LRA_UNROLL
-            for (int k = 0; k < RG::TILE; ++k) rg.mt[s][b][k] = (T)0;
+            for (int k = 0; k < RG::TILE; ++k) rg.mt[s][RG::TILE * b + k] = (T)0;
         }
     }
     rg.pw_extra = (T)0;
 }
 // a producer's power row -> this thread's two runs (as v2_mel_runs_read)
-template <class Cfg> LRA_HD void pc_runs_read(PcRegs<Cfg>& rg, Lds pwr, int tf) {
+template <class Cfg> LRA_HD void pc_runs_read(PcRegs<Cfg>& rg, Lds pwr) {
     using T = typename Cfg::real;
     constexpr int BPL = Cfg::R / 2;
     static_assert(BPL == 8, "runs of 8 bins");
     LRA_UNROLL
     for (int run = 0; run < 2; ++run) {
-        const int first = 8 * (run * Cfg::TF + tf);
-        const V4<T> lo = lds_ld<V4<T>>(pwr, v2_pw_index<Cfg>(first) * (int)sizeof(T)), hi = lds_ld<V4<T>>(pwr, v2_pw_index<Cfg>(first + 4) * (int)sizeof(T));
+        const V4<T> lo = lds_ld<V4<T>>(pwr, rg.pwa[2 * run]), hi = lds_ld<V4<T>>(pwr, rg.pwa[2 * run + 1]);
         T* d = rg.pw + run * BPL;
         d[0] = lo.a; d[1] = lo.b; d[2] = lo.c; d[3] = lo.d; d[4] = hi.a; d[5] = hi.b; d[6] = hi.c; d[7] = hi.d;
     }
-    rg.pw_extra = lds_ld<T>(pwr, (tf == 0 ? v2_pw_index<Cfg>(Cfg::M) : 0) * (int)sizeof(T));  // consumed by thread 0 only
+    rg.pw_extra = lds_ld<T>(pwr, rg.pwx);  // consumed by thread 0 only
 }
 // (wA, wB) x power, running sums along both runs -> rs[jj][tf] (as v2_mel_accumulate: same operations, same order)
 template <class Cfg> LRA_HD void pc_accumulate(const StftArgs<typename Cfg::real>& a, int tf, PcRegs<Cfg>& rg, Lds rs) {
@@ -244,7 +301,10 @@ template <class Cfg> LRA_HD void pc_accumulate(const StftArgs<typename Cfg::real
     }
 }
 // mel[m] of bands 2 tf, 2 tf + 1 for producer S's frame (as melr_combine with the register tile; `wg`: the workgroup's LDS, which rg.mad addresses)
-template <class Cfg, int S> LRA_HD void pc_combine(const StftArgs<typename Cfg::real>& a, int clip, int frame, int tf, int it, bool last_of_slot, PcRegs<Cfg>& rg, Lds wg) {
+// UNI: pc_tile_uniform holds (the tile slot is rg.ph[S][b] + it, one value per wave)
+// (producer S's tile goes in and comes out by value: written through a reference, the indexed element store keeps the whole register
+// struct in scratch memory)
+template <class Cfg, int S, bool UNI> LRA_HD PcTileV pc_combine(const StftArgs<typename Cfg::real>& a, int clip, int frame, int tf, int it, bool last_of_slot, PcRegs<Cfg>& rg, Lds wg, PcTileV mt) {
     using T = typename Cfg::real;
     using RG = PcRegs<Cfg>;
     constexpr int PH = RG::PH, NB = RG::NB, MT = RG::TILE;
@@ -253,11 +313,10 @@ template <class Cfg, int S> LRA_HD void pc_combine(const StftArgs<typename Cfg::
     for (int b = 0; b < NB; ++b) {
         LRA_UNROLL
         for (int q = 0; q < 2 * PH; ++q) {
-            const cx<T> pr = lds_ld<cx<T>>(wg, rg.mad[b][q]);
+            const cx<T> pr = pc_pair_ld(wg, rg.mad[b][q]);
             x[b][q] = q < PH ? pr.y : pr.x;
         }
     }
-    PcTile<Cfg> tile{rg.mt[S]};
     LRA_UNROLL
     for (int b = 0; b < NB; ++b) {
         const int m = NB * tf + b;
@@ -271,13 +330,57 @@ template <class Cfg, int S> LRA_HD void pc_combine(const StftArgs<typename Cfg::
             part[h] = acc;
         }
         const T v = part[0] + part[1];
-        const long long row0 = ((long long)clip * a.n_mels + m) * a.n_frames;
-        const int s8 = melr_tile_slot<Cfg, PcTile<Cfg>>(a, clip, frame, it, b, row0);
-        LRA_UNROLL
-        for (int k = 0; k < MT; ++k) rg.mt[S][b][k] = k == s8 ? v : rg.mt[S][b][k];
-        if (last_of_slot || s8 == MT - 1) melr_burst<Cfg, PcTile<Cfg>>(a, row0, frame, s8, it, b, tile);
+        int s8;
+        if constexpr (UNI) {
+            s8 = (rg.ph[S][b] + it) & (MT - 1);
+            mt[MT * b + s8] = v;
+        } else {
+            s8 = (int)((rg.row[b] - a.Mel + frame) & (MT - 1));  // (melr_tile_slot's per-lane form)
+            LRA_UNROLL
+            for (int k = 0; k < MT; ++k) mt[MT * b + k] = k == s8 ? v : mt[MT * b + k];
+        }
+        if (last_of_slot || s8 == MT - 1) {
+            T t8[MT];
+            pc_tile_band(mt, b, t8);
+            melr_burst_row(rg.row[b] + (frame - s8), s8, it, t8);
+        }
+    }
+    return mt;
+}
+
+#ifndef LRA_HOSTSIM
+// The consumer wave's loop.  Its thread index is read once, without phase_tid()'s opaque move (which is there for the producer's register
+// budget): the run offsets, the running-sum addresses, the output rows and the lane-0 test are loop invariants here and stay in registers.
+template <class Cfg, bool UNI> __device__ __forceinline__ void pc_consumer(const StftArgs<typename Cfg::real>& a, int clip, int f_first, int iters, int n_it, Lds lds) {
+    using L = PcLayout<Cfg>;
+    constexpr int TF = Cfg::TF;
+    PcRegs<Cfg> rg;
+    const Lds rs = lds_sub(lds, L::rs_off());
+    const int tf = (int)(threadIdx.x & (TF - 1));
+    pc_consumer_prologue<Cfg>(a, clip, f_first, iters, tf, rg, lds);
+    pc_fence();
+    for (int it = 0; it < n_it; ++it) {
+#define LRA_PC_SERVE(S)                                                                                                        \
+        {                                                                                                                      \
+            const int frame = f_first + S * iters + it;                                                                       \
+            v2_setprio<LRA_PC_PRIO_CA>();                                                                                      \
+            pc_wait_ready(lds, L::ready_off(S), it + 1, a.nonfinite_flag);                                                     \
+            pc_runs_read<Cfg>(rg, lds_sub(lds, L::pw_off(S)));                                                                 \
+            pc_fence();                                                                                                        \
+            if (tf == 0) pc_flag_store(lds, L::consumed_off(S), it + 1); /* behind the run reads */                            \
+            pc_fence();                                                                                                        \
+            pc_accumulate<Cfg>(a, tf, rg, rs);                                                                                 \
+            pc_fence();                                                                                                        \
+            v2_setprio<LRA_PC_PRIO_CB>();                                                                                      \
+            if (frame < a.n_frames) rg.mt[S] = pc_combine<Cfg, S, UNI>(a, clip, frame, tf, it, it + 1 == iters || frame + 1 >= a.n_frames, rg, lds, rg.mt[S]); \
+            pc_fence();                                                                                                        \
+        }
+        LRA_PC_SERVE(0)
+        LRA_PC_SERVE(1)
+#undef LRA_PC_SERVE
     }
 }
+#endif
 
 // One workgroup = NP producer slots + one consumer; slot s transforms frames f_first + s iters + it, it = 0 .. iters - 1 (as stft_block2 with FPB = NP).
 template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const StftArgs<typename Cfg::real>& a_in, const int blk, Lds lds) {
@@ -300,7 +403,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
     LRA_PHASE(L::NT, tid) {
         const int w = tid / TF, tf = tid % TF;
         if (w < NP) pc_producer_prologue<Cfg, HD>(a, clip, f_first + w * iters, tf, LRA_R(prg));
-        else pc_consumer_prologue<Cfg>(a, tf, LRA_R(crg));
+        else pc_consumer_prologue<Cfg>(a, clip, f_first, iters, tf, LRA_R(crg), lds);
         if (tid < 2 * NP) pc_flag_store(lds, L::flags_off() + 4 * tid, 0);
     } LRA_PHASE_END
     for (int it = 0; it < n_it; ++it) {
@@ -329,7 +432,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
         } LRA_PHASE_END  // (ready[s] published, C has seen it)
         for (int s = 0; s < NP; ++s) {
             LRA_PHASE(L::NT, tid) {
-                if (tid / TF == NP) pc_runs_read<Cfg>(LRA_R(crg), lds_sub(lds, L::pw_off(s)), tid % TF);
+                if (tid / TF == NP) pc_runs_read<Cfg>(LRA_R(crg), lds_sub(lds, L::pw_off(s)));
             } LRA_PHASE_END_SYNC(true)
             LRA_PHASE(L::NT, tid) {
                 if (tid / TF == NP) pc_accumulate<Cfg>(a, tid % TF, LRA_R(crg), lds_sub(lds, L::rs_off()));
@@ -338,8 +441,13 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
                 const int tf = tid % TF, frame = f_first + s * iters + it;
                 if (tid / TF == NP && frame < a.n_frames) {
                     const bool last = it + 1 == iters || frame + 1 >= a.n_frames;
-                    if (s == 0) pc_combine<Cfg, 0>(a, clip, frame, tf, it, last, LRA_R(crg), lds);
-                    else pc_combine<Cfg, 1>(a, clip, frame, tf, it, last, LRA_R(crg), lds);
+                    if (pc_tile_uniform<Cfg>(a)) {
+                        if (s == 0) LRA_R(crg).mt[0] = pc_combine<Cfg, 0, true>(a, clip, frame, tf, it, last, LRA_R(crg), lds, LRA_R(crg).mt[0]);
+                        else LRA_R(crg).mt[1] = pc_combine<Cfg, 1, true>(a, clip, frame, tf, it, last, LRA_R(crg), lds, LRA_R(crg).mt[1]);
+                    } else {
+                        if (s == 0) LRA_R(crg).mt[0] = pc_combine<Cfg, 0, false>(a, clip, frame, tf, it, last, LRA_R(crg), lds, LRA_R(crg).mt[0]);
+                        else LRA_R(crg).mt[1] = pc_combine<Cfg, 1, false>(a, clip, frame, tf, it, last, LRA_R(crg), lds, LRA_R(crg).mt[1]);
+                    }
                 }
             } LRA_PHASE_END_SYNC(true)
         }
@@ -394,36 +502,8 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
             pc_fence();
         }
     } else {
-        PcRegs<Cfg> rg;
-        const Lds rs = lds_sub(lds, L::rs_off());
-        {
-            const int tf = phase_tid() % TF;
-            pc_consumer_prologue<Cfg>(a, tf, rg);
-        }
-        pc_fence();
-        for (int it = 0; it < n_it; ++it) {
-#define LRA_PC_SERVE(S)                                                                                                        \
-            {                                                                                                                  \
-                const int frame = f_first + S * iters + it;                                                                   \
-                v2_setprio<LRA_PC_PRIO_CA>();                                                                                  \
-                pc_wait(lds, L::ready_off(S), it + 1, a.nonfinite_flag);                                                                        \
-                { const int tf = phase_tid() % TF; pc_runs_read<Cfg>(rg, lds_sub(lds, L::pw_off(S)), tf); }                    \
-                pc_fence();                                                                                                    \
-                if (phase_tid() % TF == 0) pc_flag_store(lds, L::consumed_off(S), it + 1); /* behind the run reads */          \
-                pc_fence();                                                                                                    \
-                { const int tf = phase_tid() % TF; pc_accumulate<Cfg>(a, tf, rg, rs); }                                        \
-                pc_fence();                                                                                                    \
-                v2_setprio<LRA_PC_PRIO_CB>();                                                                                  \
-                if (frame < a.n_frames) {                                                                                      \
-                    const int tf = phase_tid() % TF;                                                                           \
-                    pc_combine<Cfg, S>(a, clip, frame, tf, it, it + 1 == iters || frame + 1 >= a.n_frames, rg, lds);           \
-                }                                                                                                              \
-                pc_fence();                                                                                                    \
-            }
-            LRA_PC_SERVE(0)
-            LRA_PC_SERVE(1)
-#undef LRA_PC_SERVE
-        }
+        if (pc_tile_uniform<Cfg>(a)) pc_consumer<Cfg, true>(a, clip, f_first, iters, n_it, lds);
+        else pc_consumer<Cfg, false>(a, clip, f_first, iters, n_it, lds);
     }
 #endif
 }
