@@ -277,6 +277,30 @@ int lra_pcen_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int64
  * [outer][n_bands][inner] of `dtype` (device), the filter runs over n_bands: out[m] = max(S[m - size/2 .. m - size/2 + size - 1]). */
 int lra_maxfilter_exec(lra_ctx* ctx, const void* S, void* out, int64_t outer, int n_bands, int64_t inner, int size, int dtype);
 
+/* ---- onset strength: librosa.onset.onset_strength / onset_strength_multi, librosa/onset.py:217-367, 445-645 ----------------------- */
+#define LRA_ONSET_NONE 0    /* aggregate=False (not callable): one row per band (:619-622) */
+#define LRA_ONSET_MEAN 1    /* np.mean over each channel's bands (util.sync, util/utils.py:1785-1814; :612-622) */
+#define LRA_ONSET_SUM 2
+#define LRA_ONSET_MAX 3
+#define LRA_ONSET_MIN 4
+#define LRA_ONSET_MEDIAN 5  /* exact np.median: the mean of the two middle values for an even count */
+#define LRA_ONSET_ROWS 6    /* S already holds the aggregated rows (a host-side aggregate callable): pad, trim and detrend only */
+/* S: [batch][n_bands][n_frames] of `dtype` (device), the mel kernel's layout.  fuse_db != 0: S is a power spectrogram and the flux is
+ * taken of power_to_db(|S|, ref=1, amin, top_db) (:579-583), evaluated while S is read; item_max (device, [batch]) is the per-item max
+ * of |S| (lra_item_max_exec).  Otherwise S is used as given (:585-589).  ref: the caller's reference of S's shape, used as given (:601-604),
+ * or NULL: S itself (max_size == 1) or maximum_filter1d(S, max_size, axis=bands, mode="reflect") (:594-600).
+ *   env[b][m][t] = max(0, S[b][m][t + lag] - ref[b][m][t]),  0 <= t < n_frames - lag (:606-610)
+ * Aggregates run over channels: channel c holds the bands ch_bands[ch_offsets[c] .. ch_offsets[c + 1]) (device int32 arrays;
+ * max_ch_bands = the largest channel's band count), or both NULL: one channel of every band in order (channels=None; n_ch = 1,
+ * max_ch_bands = n_bands); NONE / ROWS write one row per band and ignore them.
+ * out: [batch][rows][n_out], rows = n_ch (aggregates) or n_bands; out[.][.][j] = agg(env)[j - pad] where that index lies in the
+ * envelope, 0 elsewhere (the left padding and the trim of :624-642).  detrend != 0: out is FLOAT64, scipy.signal.lfilter([1, -1],
+ * [1, -0.99], ., axis=-1) of those rows from a zero state (:635-638); env (device) is scratch of batch * rows * n_out elements of
+ * `dtype`.  Empty channels: NaN for mean / median, 0 for sum; max / min reject them (np.max raises). */
+int lra_onset_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int64_t batch, int n_bands, int64_t n_frames, int dtype, int lag, int max_size, int aggregate,
+                   const int32_t* ch_offsets, const int32_t* ch_bands, int n_ch, int max_ch_bands, int64_t pad, int64_t n_out, int fuse_db, double amin, double top_db,
+                   const void* item_max, int detrend, void* env);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

@@ -95,6 +95,8 @@ SIGNATURES = {
     "lra_griffinlim_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_int]),
     "lra_pcen_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p, c_double, c_void_p]),
     "lra_maxfilter_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int]),
+    "lra_onset_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
+                               c_double, c_double, c_void_p, c_int, c_void_p]),
     "lra_fir_decimate_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int]),
     "lra_resample_poly_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_int]),
     "lra_resample_fft_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int]),
@@ -525,6 +527,16 @@ class Context:
 
     def maxfilter_exec(self, s_ptr, out_ptr, outer, n_bands, inner, size, dtype):
         _check(self.lib.lra_maxfilter_exec(self.handle, c_void_p(s_ptr), c_void_p(out_ptr), outer, n_bands, inner, int(size), dtype_code(dtype)))
+
+    def onset_exec(self, s_ptr, ref_ptr, out_ptr, batch, n_bands, n_frames, dtype, lag, max_size, aggregate, ch_off_ptr, ch_band_ptr, n_ch, max_ch_bands, pad, n_out,
+                   item_max_ptr=None, amin=1e-10, top_db=80.0, detrend_env_ptr=None):
+        """Spectral-flux onset envelope (``include/librosa_amd.h``: lra_onset_exec).  ``item_max_ptr`` given: ``S`` is a power spectrogram whose
+        decibels (``power_to_db(|S|, amin=amin, top_db=top_db)``) are taken on the fly; ``detrend_env_ptr`` given: the rows are detrended into
+        a float64 ``out`` through that scratch."""
+        _check(self.lib.lra_onset_exec(self.handle, c_void_p(s_ptr), c_void_p(ref_ptr or None), c_void_p(out_ptr), int(batch), int(n_bands), int(n_frames), dtype_code(dtype), int(lag),
+                                       int(max_size), int(aggregate), c_void_p(ch_off_ptr or None), c_void_p(ch_band_ptr or None), int(n_ch), int(max_ch_bands), int(pad), int(n_out),
+                                       int(item_max_ptr is not None), float(amin), float(top_db), c_void_p(item_max_ptr or None), int(detrend_env_ptr is not None),
+                                       c_void_p(detrend_env_ptr or None)))
 
     def fir_decimate_exec(self, x_ptr, out_ptr, batch, n_in, n_out, taps_ptr, n_taps, down, first, div, mul, dtype):
         _check(self.lib.lra_fir_decimate_exec(self.handle, c_void_p(x_ptr), c_void_p(out_ptr), batch, n_in, n_out, c_void_p(taps_ptr), int(n_taps), int(down), int(first), float(div),

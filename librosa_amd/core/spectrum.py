@@ -402,7 +402,8 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
     """kind in {"stft", "power", "mel"}.  Returns the result laid out like the reference's.
 
     ``post(sess, mel_ptr, batch, n_mels, n_frames, real) -> (handle, rows)`` (mel only) chains further device work on the mel
-    spectrogram before anything is downloaded (``feature.mfcc``); the result then has ``rows`` rows instead of ``n_mels``."""
+    spectrogram before anything is downloaded (``feature.mfcc``); the result then has ``rows`` rows instead of ``n_mels``.  ``post`` may
+    return ``(handle, rows, cols)`` when its result has ``cols`` columns instead of ``n_frames`` (``onset.onset_strength_multi``)."""
     need_device_check = _validate_audio(y, check_finite)
     y, hop, fft_window, center, pad_mode = _prepare_stft(y, n_fft, hop_length, win_length, window, center, pad_mode)
     in_dtype = _arrays.numpy_dtype_of(y)
@@ -526,7 +527,9 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
             ptr, handle = sess.output((batch, n_mels, n_frames), real)
             ctx.melspectrogram_exec(plan, mel_plan, y_ptr, batch, n, y_stride, power, ptr)
             if post is not None:
-                handle, n_mels = post(sess, ptr, batch, n_mels, n_frames, real)
+                handle, n_mels, *cols = post(sess, ptr, batch, n_mels, n_frames, real)
+                if cols:
+                    n_frames = int(cols[0])
         if need_device_check and ctx.nonfinite_read():
             # the flag says "some frame's DC bin is not finite"; finite samples of enormous magnitude overflow it
             # too, so the samples themselves decide (util.valid_audio tests np.isfinite(y), util/utils.py:305)

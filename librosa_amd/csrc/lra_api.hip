@@ -40,6 +40,7 @@
 #include "lra_mel.h"
 #include "lra_post.h"
 #include "lra_pcen.h"
+#include "lra_onset.h"
 #include "lra_cqt.h"
 #include "lra_hpss.h"
 #include "lra_probe.h"
@@ -2902,6 +2903,97 @@ int lra_maxfilter_exec(lra_ctx* ctx, const void* S, void* out, int64_t outer, in
         hipLaunchKernelGGL(maxfilter_bands_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)S, (float*)out, (long long)outer, n_bands, (long long)inner, size);
     LRA_HIP(hipGetLastError());
     return LRA_OK;
+}
+
+// ---- onset strength (lra_onset.h) -------------------------------------------------------------------------------------------
+static_assert(kOnsetNone == LRA_ONSET_NONE && kOnsetMean == LRA_ONSET_MEAN && kOnsetSum == LRA_ONSET_SUM && kOnsetMax == LRA_ONSET_MAX && kOnsetMin == LRA_ONSET_MIN &&
+                  kOnsetMedian == LRA_ONSET_MEDIAN && kOnsetRows == LRA_ONSET_ROWS,
+              "onset aggregation codes");
+extern "C++" {  // (the launch templates; this part of the file is the C ABI)
+namespace {
+template <class T, bool DB>
+int onset_run(lra_ctx* ctx, OnsetArgs<T> a, int aggregate, int max_ch_bands, int detrend, void* env, void* out) {
+    const int rows = (aggregate == kOnsetNone || aggregate == kOnsetRows) ? a.n_bands : a.n_ch;
+    a.out = detrend ? (T*)env : (T*)out;
+    if (aggregate == kOnsetMedian) {
+        const int fb = onset_median_frames(max_ch_bands, sizeof(T));
+        const long long grid = a.batch * ((a.n_out + fb - 1) / fb);
+        if (grid > 0x7fffffffLL) return fail(LRA_EINVAL, "onset: too many frames for one launch");
+        const size_t lds = (size_t)(max_ch_bands > 0 ? max_ch_bands : 1) * fb * sizeof(T);
+        const void* kern = reinterpret_cast<const void*>(&onset_median_kernel<T, DB>);
+        if (lds > 65536) LRA_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((onset_median_kernel<T, DB>), dim3((unsigned)grid), dim3(fb), lds, ctx->stream, a);
+    } else {
+        const long long grid = a.batch * ((a.n_out + 255) / 256);
+        if (grid > 0x7fffffffLL) return fail(LRA_EINVAL, "onset: too many frames for one launch");
+#define LRA_ONSET(AGG) hipLaunchKernelGGL((onset_flux_kernel<T, DB, AGG>), dim3((unsigned)grid), dim3(256), 0, ctx->stream, a)
+        switch (aggregate) {
+            case kOnsetNone: LRA_ONSET(kOnsetNone); break;
+            case kOnsetMean: LRA_ONSET(kOnsetMean); break;
+            case kOnsetSum: LRA_ONSET(kOnsetSum); break;
+            case kOnsetMax: LRA_ONSET(kOnsetMax); break;
+            case kOnsetMin: LRA_ONSET(kOnsetMin); break;
+            default: LRA_ONSET(kOnsetRows); break;
+        }
+#undef LRA_ONSET
+    }
+    LRA_HIP(hipGetLastError());
+    if (detrend) {
+        const long long n_rows = a.batch * rows;
+        const long long grid = (n_rows + kOnsetDetrendRows - 1) / kOnsetDetrendRows;
+        if (grid > 0x7fffffffLL) return fail(LRA_EINVAL, "onset: too many rows for one launch");
+        hipLaunchKernelGGL(onset_detrend_kernel<T>, dim3((unsigned)grid), dim3(64), 0, ctx->stream, (const T*)env, (double*)out, n_rows, (long long)a.n_out);
+        LRA_HIP(hipGetLastError());
+    }
+    return LRA_OK;
+}
+
+template <class T>
+int onset_dispatch(lra_ctx* ctx, const void* S, const void* ref, void* out, int64_t batch, int n_bands, int64_t n_frames, int lag, int max_size, int aggregate, const int32_t* ch_offsets,
+                   const int32_t* ch_bands, int n_ch, int max_ch_bands, int64_t pad, int64_t n_out, int fuse_db, double amin, double top_db, const void* item_max, int detrend, void* env) {
+    OnsetArgs<T> a;
+    a.S = (const T*)S;
+    a.ref = (const T*)ref;
+    a.out = nullptr;
+    a.ch_off = ch_offsets;
+    a.ch_band = ch_bands;
+    a.batch = batch;
+    a.n_frames = n_frames;
+    a.pad = pad;
+    a.n_out = n_out;
+    a.n_bands = n_bands;
+    a.lag = aggregate == kOnsetRows ? 0 : lag;
+    a.max_size = max_size;
+    a.n_ch = n_ch;
+    a.db = DbArgs<T>{(T)amin, (T)1, nullptr, (const T*)item_max, (T)top_db};
+    return fuse_db ? onset_run<T, true>(ctx, a, aggregate, max_ch_bands, detrend, env, out) : onset_run<T, false>(ctx, a, aggregate, max_ch_bands, detrend, env, out);
+}
+}  // namespace
+}  // extern "C++"
+
+int lra_onset_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int64_t batch, int n_bands, int64_t n_frames, int dtype, int lag, int max_size, int aggregate,
+                   const int32_t* ch_offsets, const int32_t* ch_bands, int n_ch, int max_ch_bands, int64_t pad, int64_t n_out, int fuse_db, double amin, double top_db,
+                   const void* item_max, int detrend, void* env) {
+    LRA_BIND(ctx);
+    if (aggregate < LRA_ONSET_NONE || aggregate > LRA_ONSET_ROWS) return fail(LRA_EINVAL, "onset: unknown aggregate code");
+    if (aggregate != LRA_ONSET_ROWS && (lag < 1 || max_size < 1)) return fail(LRA_EINVAL, "onset: lag and max_size must be positive integers");
+    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "onset: dtype must be LRA_F32 or LRA_F64");
+    if (n_bands < 0 || n_frames < 0 || pad < 0 || n_ch < 0) return fail(LRA_EINVAL, "onset: negative size");
+    const bool per_band = aggregate == LRA_ONSET_NONE || aggregate == LRA_ONSET_ROWS;
+    if (batch <= 0 || n_out <= 0 || (per_band ? n_bands : n_ch) == 0) return LRA_OK;
+    if (!S || !out) return fail(LRA_EINVAL, "null data pointer");
+    if (n_bands == 0) return fail(LRA_EINVAL, "onset: channels over an empty band axis");
+    if (!per_band && (!ch_offsets != !ch_bands || max_ch_bands < 0)) return fail(LRA_EINVAL, "onset: give both channel tables or neither");
+    if (!per_band && !ch_offsets && (n_ch != 1 || max_ch_bands != n_bands)) return fail(LRA_EINVAL, "onset: without channel tables there is one channel of every band");
+    if (fuse_db && (!(amin > 0) || top_db < 0 || !item_max)) return fail(LRA_EINVAL, "onset: the decibel step needs amin > 0, top_db >= 0 and the per-item maxima");
+    if (aggregate == LRA_ONSET_ROWS && fuse_db) return fail(LRA_EINVAL, "onset: finished rows take no decibel step");
+    if (detrend && !env) return fail(LRA_EINVAL, "onset: detrend needs the envelope scratch");
+    if (aggregate == LRA_ONSET_MEDIAN && onset_median_frames(max_ch_bands, real_bytes(dtype)) == 0)
+        return fail(LRA_EINVAL, "onset: a median channel of " + std::to_string(max_ch_bands) + " bands does not fit the 160 KiB LDS of a CU");
+    return dtype == LRA_F64 ? onset_dispatch<double>(ctx, S, ref, out, batch, n_bands, n_frames, lag, max_size, aggregate, ch_offsets, ch_bands, n_ch, max_ch_bands, pad, n_out, fuse_db,
+                                                     amin, top_db, item_max, detrend, env)
+                            : onset_dispatch<float>(ctx, S, ref, out, batch, n_bands, n_frames, lag, max_size, aggregate, ch_offsets, ch_bands, n_ch, max_ch_bands, pad, n_out, fuse_db,
+                                                    amin, top_db, item_max, detrend, env);
 }
 
 int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch, int64_t n_in, int64_t n_out, const void* taps, int n_taps, int down, int first, double div, double mul,

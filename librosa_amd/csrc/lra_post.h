@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "lra_db.h"
+
 namespace lra {
 
 // ---- per-item maximum of |x| (the reduction behind ref=np.max and top_db) --------------------------------------------
@@ -51,34 +53,9 @@ template <class T, bool ABS> __global__ __launch_bounds__(256) void item_absmax_
     if (threadIdx.x == 0) atomicMax(&out[item], MaxBits<T>::bits(red[0]));
 }
 
-// ---- decibel scaling ---------------------------------------------------------------------------------------------------
+// ---- decibel scaling (the arithmetic itself is in lra_db.h, shared with the onset kernels) -------------------------------
 // AMP: the input is an amplitude (amplitude_to_db squares it first, in the input precision, exactly as the reference does:
 // power_to_db(S**2, ref=ref**2, amin=amin**2), core/spectrum.py:2030-2037)
-template <class T> __device__ __forceinline__ T ten_log10(T v) { return (T)10 * log10(v); }
-template <> __device__ __forceinline__ float ten_log10<float>(float v) { return 10.0f * log10f(v); }
-
-template <class T> struct DbArgs {
-    T amin;               // power domain (the host squares amplitude_to_db's amin)
-    T ref_scalar;         // |ref| when ref_items == nullptr (input domain: squared here for amplitudes)
-    const T* ref_items;   // per-item |reference| values (input domain), or nullptr
-    const T* item_max;    // per-item max of |x| (input domain), or nullptr when top_db is None
-    T top_db;
-};
-
-template <class T> __device__ __forceinline__ T db_of(T mag, T amin, T ref_db) { return ten_log10<T>(mag > amin ? mag : amin) - ref_db; }
-
-template <class T> __device__ __forceinline__ void db_item_constants(const DbArgs<T>& d, long long item, bool amp, T& ref_db, T& floor_db) {
-    T ref = d.ref_items ? d.ref_items[item] : d.ref_scalar;
-    if (amp) ref = ref * ref;
-    ref_db = ten_log10<T>(ref > d.amin ? ref : d.amin);
-    floor_db = -INFINITY;
-    if (d.item_max) {
-        T mx = d.item_max[item];
-        if (amp) mx = mx * mx;
-        floor_db = db_of<T>(mx, d.amin, ref_db) - d.top_db;  // log10 is monotone: max of the logs = log of the max
-    }
-}
-
 template <class T, bool AMP> __global__ __launch_bounds__(256) void to_db_kernel(const T* __restrict__ x, T* __restrict__ out, long long per_item, int chunks_per_item, DbArgs<T> d) {
     const long long item = blockIdx.x / chunks_per_item;
     const int chunk = blockIdx.x % chunks_per_item;

@@ -1,0 +1,148 @@
+// onsetsim.cpp -- runs the onset-strength kernel bodies of librosa_amd/csrc/lra_onset.h on host threads.
+//
+// TEST INFRASTRUCTURE ONLY.  Built by tests/test_onset_host.py (g++ -DLRA_POSTSIM -pthread) into tests/hostsim/_onsetsim.so.  One OS
+// thread per lane of a workgroup, __syncthreads() is a barrier across them, __shared__ is a static the lanes share; workgroups run one
+// after the other.  Never linked into, imported by, or used as a fallback for the product library.
+#define LRA_POSTSIM 1
+#include <cmath>
+#include <condition_variable>
+#include <cstddef>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+struct SimIdx { unsigned x = 0, y = 0, z = 0; };
+static thread_local SimIdx threadIdx;
+static thread_local SimIdx blockIdx;
+static thread_local SimIdx blockDim;
+
+namespace {
+struct Barrier {
+    std::mutex m;
+    std::condition_variable cv;
+    int n = 0, waiting = 0;
+    unsigned long long gen = 0;
+    void wait() {
+        std::unique_lock<std::mutex> lk(m);
+        const unsigned long long g = gen;
+        if (++waiting == n) {
+            waiting = 0;
+            ++gen;
+            cv.notify_all();
+        } else {
+            cv.wait(lk, [&] { return gen != g; });
+        }
+    }
+};
+Barrier g_barrier;
+}  // namespace
+static inline void __syncthreads() { g_barrier.wait(); }
+
+#define __global__
+#define __device__
+#define __forceinline__ inline
+#define __shared__ static
+#define __launch_bounds__(...)
+using std::exp;
+using std::expm1;
+using std::log;
+using std::log10;
+using std::log1p;
+using std::pow;
+
+alignas(16) static unsigned char g_postsim_dyn_lds[160 * 1024];  // the dynamic LDS of the workgroup being run
+
+#include "../../librosa_amd/csrc/lra_onset.h"
+
+namespace {
+template <class F> void run_grid(unsigned grid, unsigned block, F body) {
+    g_barrier.n = (int)block;
+    for (unsigned b = 0; b < grid; ++b) {
+        std::vector<std::thread> lanes;
+        for (unsigned t = 0; t < block; ++t)
+            lanes.emplace_back([=] {
+                threadIdx.x = t;
+                blockIdx.x = b;
+                blockDim.x = block;
+                body();
+            });
+        for (auto& l : lanes) l.join();
+    }
+}
+// kernels without __syncthreads (each lane owns its LDS column): the lanes of a workgroup one after the other on the calling thread
+template <class F> void run_grid_serial(unsigned grid, unsigned block, F body) {
+    for (unsigned b = 0; b < grid; ++b)
+        for (unsigned t = 0; t < block; ++t) {
+            threadIdx.x = t;
+            blockIdx.x = b;
+            blockDim.x = block;
+            body();
+        }
+}
+
+// the launches of onset_run (lra_api.hip): same geometry, same kernel selection
+template <class T, bool DB>
+int sim_run(lra::OnsetArgs<T> a, int aggregate, int max_ch_bands, int detrend, void* env, void* out) {
+    using namespace lra;
+    const int rows = (aggregate == kOnsetNone || aggregate == kOnsetRows) ? a.n_bands : a.n_ch;
+    a.out = detrend ? (T*)env : (T*)out;
+    if (aggregate == kOnsetMedian) {
+        const int fb = onset_median_frames(max_ch_bands, sizeof(T));
+        if (fb == 0) return -1;
+        const unsigned grid = (unsigned)(a.batch * ((a.n_out + fb - 1) / fb));
+        run_grid_serial(grid, (unsigned)fb, [=] { onset_median_kernel<T, DB>(a); });
+    } else {
+        const unsigned grid = (unsigned)(a.batch * ((a.n_out + 255) / 256));
+        switch (aggregate) {
+            case kOnsetNone: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetNone>(a); }); break;
+            case kOnsetMean: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetMean>(a); }); break;
+            case kOnsetSum: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetSum>(a); }); break;
+            case kOnsetMax: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetMax>(a); }); break;
+            case kOnsetMin: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetMin>(a); }); break;
+            default: run_grid_serial(grid, 256, [=] { onset_flux_kernel<T, DB, kOnsetRows>(a); }); break;
+        }
+    }
+    if (detrend) {
+        const long long n_rows = a.batch * rows;
+        const unsigned grid = (unsigned)((n_rows + kOnsetDetrendRows - 1) / kOnsetDetrendRows);
+        const T* e = (const T*)env;
+        double* o = (double*)out;
+        const long long n = a.n_out;
+        run_grid(grid, 64, [=] { onset_detrend_kernel<T>(e, o, n_rows, n); });
+    }
+    return 0;
+}
+
+template <class T>
+int sim_dispatch(const void* S, const void* ref, void* out, long long batch, int n_bands, long long n_frames, int lag, int max_size, int aggregate, const int* ch_off, const int* ch_band,
+                 int n_ch, int max_ch_bands, long long pad, long long n_out, int fuse_db, double amin, double top_db, const void* item_max, int detrend, void* env) {
+    lra::OnsetArgs<T> a;
+    a.S = (const T*)S;
+    a.ref = (const T*)ref;
+    a.out = nullptr;
+    a.ch_off = ch_off;
+    a.ch_band = ch_band;
+    a.batch = batch;
+    a.n_frames = n_frames;
+    a.pad = pad;
+    a.n_out = n_out;
+    a.n_bands = n_bands;
+    a.lag = aggregate == lra::kOnsetRows ? 0 : lag;
+    a.max_size = max_size;
+    a.n_ch = n_ch;
+    a.db = lra::DbArgs<T>{(T)amin, (T)1, nullptr, (const T*)item_max, (T)top_db};
+    return fuse_db ? sim_run<T, true>(a, aggregate, max_ch_bands, detrend, env, out) : sim_run<T, false>(a, aggregate, max_ch_bands, detrend, env, out);
+}
+}  // namespace
+
+extern "C" {
+// the arguments of lra_onset_exec (include/librosa_amd.h), host pointers
+int onsetsim_exec(const void* S, const void* ref, void* out, long long batch, int n_bands, long long n_frames, int is_f64, int lag, int max_size, int aggregate, const int* ch_off,
+                  const int* ch_band, int n_ch, int max_ch_bands, long long pad, long long n_out, int fuse_db, double amin, double top_db, const void* item_max, int detrend, void* env) {
+    if (batch <= 0 || n_out <= 0) return 0;
+    return is_f64 ? sim_dispatch<double>(S, ref, out, batch, n_bands, n_frames, lag, max_size, aggregate, ch_off, ch_band, n_ch, max_ch_bands, pad, n_out, fuse_db, amin, top_db, item_max,
+                                         detrend, env)
+                  : sim_dispatch<float>(S, ref, out, batch, n_bands, n_frames, lag, max_size, aggregate, ch_off, ch_band, n_ch, max_ch_bands, pad, n_out, fuse_db, amin, top_db, item_max,
+                                        detrend, env);
+}
+}
