@@ -301,6 +301,27 @@ int lra_onset_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int6
                    const int32_t* ch_offsets, const int32_t* ch_bands, int n_ch, int max_ch_bands, int64_t pad, int64_t n_out, int fuse_db, double amin, double top_db,
                    const void* item_max, int detrend, void* env);
 
+/* ---- tempogram and tempo: librosa.feature.tempogram / tempo, librosa/feature/rhythm.py:38-191, 295-471 ------------------------------ */
+#define LRA_TEMPOGRAM_WRITE 0   /* the normalised tempogram, out: float64 [batch][win_length][n_frames] (:173-191) */
+#define LRA_TEMPOGRAM_SUM 1     /* tempo(aggregate=np.mean), out: float64 [batch] BPM (:445-471) */
+#define LRA_TEMPOGRAM_ARGMAX 2  /* tempo(aggregate=None), out: float64 [batch][n_frames] BPM per frame */
+#define LRA_TEMPOGRAM_NORM_NONE 0
+#define LRA_TEMPOGRAM_NORM_INF 1
+#define LRA_TEMPOGRAM_NORM_L1 2
+#define LRA_TEMPOGRAM_NORM_L2 3
+/* Bytes of device scratch `work` that lra_tempogram_exec needs for these sizes (n_frames: the tempogram's frame count). */
+int64_t lra_tempogram_work_bytes(int64_t batch, int64_t n_frames, int win_length, int mode);
+/* env: [batch][n] onset envelopes of `dtype` (device).  center != 0: np.pad(env, win_length // 2, mode="linear_ramp", end_values=0) and
+ * the first n frames (:167-182), else n - win_length + 1 frames (n >= win_length).  Each frame of hop 1 times window (device float64
+ * [win_length], get_window(window, win_length, fftbins=True)) is autocorrelated in float64 up to lag win_length - 1 (core/audio.py:1320-1394)
+ * and normalised per column by util.normalize(norm, axis=-2) with threshold tiny and fill=None (util/utils.py:797-1020).
+ * SUM / ARGMAX then score log1p(1e6 tg) + logprior (device float64 [win_length]) and take np.argmax's index (the first NaN, else the first
+ * maximum) into bpms (device float64 [win_length]): SUM on the mean over frames (group sums added in a fixed order, then / n_frames),
+ * ARGMAX per frame.  work: device scratch of lra_tempogram_work_bytes bytes.  nonfinite (host, may be NULL): set to 1 when some column of
+ * the autocorrelation is not finite (normalize raises for every norm, :865-866) -- reading it waits for the stream. */
+int lra_tempogram_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, int win_length, int center, const void* window, int norm, int mode,
+                       const void* logprior, const void* bpms, void* out, void* work, int* nonfinite);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

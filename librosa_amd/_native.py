@@ -97,6 +97,8 @@ SIGNATURES = {
     "lra_maxfilter_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int]),
     "lra_onset_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
                                c_double, c_double, c_void_p, c_int, c_void_p]),
+    "lra_tempogram_work_bytes": (c_int64, [c_int64, c_int64, c_int, c_int]),
+    "lra_tempogram_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_fir_decimate_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int]),
     "lra_resample_poly_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_int]),
     "lra_resample_fft_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int]),
@@ -537,6 +539,17 @@ class Context:
                                        int(max_size), int(aggregate), c_void_p(ch_off_ptr or None), c_void_p(ch_band_ptr or None), int(n_ch), int(max_ch_bands), int(pad), int(n_out),
                                        int(item_max_ptr is not None), float(amin), float(top_db), c_void_p(item_max_ptr or None), int(detrend_env_ptr is not None),
                                        c_void_p(detrend_env_ptr or None)))
+
+    def tempogram_work_bytes(self, batch, n_frames, win_length, mode):
+        return int(self.lib.lra_tempogram_work_bytes(int(batch), int(n_frames), int(win_length), int(mode)))
+
+    def tempogram_exec(self, env_ptr, batch, n, dtype, win_length, center, window_ptr, norm, mode, logprior_ptr, bpms_ptr, out_ptr, work_ptr):
+        """Autocorrelation tempogram / tempo of [batch][n] envelopes (``include/librosa_amd.h``: lra_tempogram_exec).  Returns True when a
+        column of the autocorrelation is not finite (this waits for the stream)."""
+        flag = c_int(0)
+        _check(self.lib.lra_tempogram_exec(self.handle, c_void_p(env_ptr), int(batch), int(n), dtype_code(dtype), int(win_length), int(bool(center)), c_void_p(window_ptr), int(norm),
+                                           int(mode), c_void_p(logprior_ptr or None), c_void_p(bpms_ptr or None), c_void_p(out_ptr), c_void_p(work_ptr), byref(flag)))
+        return bool(flag.value)
 
     def fir_decimate_exec(self, x_ptr, out_ptr, batch, n_in, n_out, taps_ptr, n_taps, down, first, div, mul, dtype):
         _check(self.lib.lra_fir_decimate_exec(self.handle, c_void_p(x_ptr), c_void_p(out_ptr), batch, n_in, n_out, c_void_p(taps_ptr), int(n_taps), int(down), int(first), float(div),

@@ -45,6 +45,19 @@ def fft_frequencies(*, sr=22050, n_fft=2048):
     return np.fft.rfftfreq(n=n_fft, d=1.0 / sr)
 
 
+def tempo_frequencies(n_bins, *, hop_length=512, sr=22050):
+    """BPM of each lag of an autocorrelation tempogram; bin 0 is ``inf`` (``librosa/core/convert.py:1514-1544``)."""
+    bin_frequencies = np.zeros(int(n_bins), dtype=np.float64)
+    bin_frequencies[0] = np.inf
+    bin_frequencies[1:] = 60.0 * sr / (hop_length * np.arange(1.0, n_bins))
+    return bin_frequencies
+
+
+def fourier_tempo_frequencies(*, sr=22050, win_length=384, hop_length=512):
+    """BPM of each bin of a Fourier tempogram (``librosa/core/convert.py:1547-1579``)."""
+    return fft_frequencies(sr=sr * 60 / float(hop_length), n_fft=win_length)
+
+
 def mel_frequencies(n_mels=128, *, fmin=0.0, fmax=11025.0, htk=False):
     lo = hz_to_mel(fmin, htk=htk)
     hi = hz_to_mel(fmax, htk=htk)

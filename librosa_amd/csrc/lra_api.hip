@@ -46,6 +46,7 @@
 #include "lra_probe.h"
 #include "lra_rng.h"
 #include "lra_mixed_launch.h"
+#include "lra_rhythm_launch.h"
 
 using namespace lra;
 
@@ -2994,6 +2995,79 @@ int lra_onset_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int6
                                                      amin, top_db, item_max, detrend, env)
                             : onset_dispatch<float>(ctx, S, ref, out, batch, n_bands, n_frames, lag, max_size, aggregate, ch_offsets, ch_bands, n_ch, max_ch_bands, pad, n_out, fuse_db,
                                                     amin, top_db, item_max, detrend, env);
+}
+
+// ---- tempogram / tempo (lra_rhythm.h, launched from lra_rhythm_inst.hip) ------------------------------------------------------------
+static_assert(rhythm::kWrite == LRA_TEMPOGRAM_WRITE && rhythm::kSum == LRA_TEMPOGRAM_SUM && rhythm::kArgmax == LRA_TEMPOGRAM_ARGMAX && rhythm::kNormNone == LRA_TEMPOGRAM_NORM_NONE &&
+                  rhythm::kNormInf == LRA_TEMPOGRAM_NORM_INF && rhythm::kNormL1 == LRA_TEMPOGRAM_NORM_L1 && rhythm::kNormL2 == LRA_TEMPOGRAM_NORM_L2,
+              "tempogram codes");
+static_assert(rhythm::transform_length(344) == 720 && rhythm::transform_length(384) == 800 && rhythm::transform_length(689) == 1440 && rhythm::transform_length(800) == 1600 &&
+                  rhythm::transform_length(2400) == 4800 && rhythm::transform_length(2401) == 0,
+              "tempogram transform lengths");
+
+int64_t lra_tempogram_work_bytes(int64_t batch, int64_t n_frames, int win_length, int mode) {
+    const int64_t groups = n_frames > 0 ? (n_frames + rhythm::kRhythmGroup - 1) / rhythm::kRhythmGroup : 0;
+    return 16 + (mode == LRA_TEMPOGRAM_SUM && batch > 0 && win_length > 0 ? batch * groups * (int64_t)win_length * 8 : 0);
+}
+
+int lra_tempogram_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, int win_length, int center, const void* window, int norm, int mode,
+                       const void* logprior, const void* bpms, void* out, void* work, int* nonfinite) {
+    LRA_BIND(ctx);
+    if (nonfinite) *nonfinite = 0;
+    if (mode < LRA_TEMPOGRAM_WRITE || mode > LRA_TEMPOGRAM_ARGMAX) return fail(LRA_EINVAL, "tempogram: unknown mode");
+    if (norm < LRA_TEMPOGRAM_NORM_NONE || norm > LRA_TEMPOGRAM_NORM_L2) return fail(LRA_EINVAL, "tempogram: unknown norm code");
+    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "tempogram: dtype must be LRA_F32 or LRA_F64");
+    if (win_length < 1) return fail(LRA_EINVAL, "tempogram: win_length must be a positive integer");
+    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "tempogram: negative size");
+    const int pad = center ? win_length / 2 : 0;
+    if (n + 2 * (int64_t)pad < win_length)
+        return fail(LRA_EINVAL, "tempogram: input is too short (n=" + std::to_string(n + 2 * (int64_t)pad) + ") for frame_length=" + std::to_string(win_length));
+    const int64_t n_frames = center ? n : n - win_length + 1;
+    if (batch == 0 || n_frames == 0) return LRA_OK;
+    if (!env || !window || !out || !work) return fail(LRA_EINVAL, "null data pointer");
+    if (mode != LRA_TEMPOGRAM_WRITE && (!logprior || !bpms)) return fail(LRA_EINVAL, "tempogram: tempo modes need the prior and the BPM table");
+    if (n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames per clip");
+    const int N = rhythm::transform_length(win_length);
+    if (rhythm::lds_layout(N, win_length, mode, false).total > rhythm::kRhythmLdsMax)
+        return fail(LRA_EINVAL, "tempogram: win_length=" + std::to_string(win_length) + " does not fit the LDS of a workgroup");
+    rhythm::Args a{};
+    a.env = env;
+    a.env_f64 = dtype == LRA_F64;
+    a.n = n;
+    a.n_frames = n_frames;
+    a.W = win_length;
+    a.pad = pad;
+    a.N = N;
+    a.win = (const double*)window;
+    if (N > 0) {
+        auto& tw = ctx->cqt_tw[std::make_pair(N, (int)LRA_F64)];
+        if (!tw.first) LRA_TRY(mixed_tables(N, LRA_F64, &tw.first, &tw.second));
+        a.tw_m = (const mixed::cpx<double>*)tw.first;
+        a.tw_n = (const mixed::cpx<double>*)tw.second;
+    }
+    a.norm = norm;
+    a.mode = mode;
+    a.tile = mode == LRA_TEMPOGRAM_WRITE && rhythm::lds_layout(N, win_length, mode, true).total <= rhythm::kRhythmLdsMax;
+    a.logprior = (const double*)logprior;
+    a.bpms = (const double*)bpms;
+    a.out = (double*)out;
+    a.flag = (int*)work;
+    a.partial = (double*)((char*)work + 16);
+    a.groups = (int)((n_frames + rhythm::kRhythmGroup - 1) / rhythm::kRhythmGroup);
+    if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames for one launch");
+    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
+    LRA_HIP(rhythm::launch_tempogram(a, batch, ctx->stream));
+    if (mode == LRA_TEMPOGRAM_SUM) {
+        rhythm::FinishArgs f{a.partial, a.logprior, a.bpms, a.out, n_frames, a.groups, win_length};
+        LRA_HIP(rhythm::launch_tempo_finish(f, batch, ctx->stream));
+    }
+    if (nonfinite) {
+        int h = 0;
+        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        LRA_HIP(hipStreamSynchronize(ctx->stream));
+        *nonfinite = h != 0;
+    }
+    return LRA_OK;
 }
 
 int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch, int64_t n_in, int64_t n_out, const void* taps, int n_taps, int down, int first, double div, double mul,

@@ -149,10 +149,16 @@ def _envelope(sess, s_ptr, ref_ptr, batch, n_bands, n_frames, real, job, item_ma
         off_ptr = sess.input_raw(_spectrum._as_like(sess, off), np.int32)
         band_ptr = sess.input_raw(_spectrum._as_like(sess, idx), np.int32)
     out_dtype = np.dtype(np.float64) if job["detrend"] else real
-    out_ptr, handle = sess.output((batch, rows, n_out), out_dtype)
+    stage = job.get("stage")
+    if stage is None:
+        out_ptr, handle = sess.output((batch, rows, n_out), out_dtype)
+    else:
+        out_ptr = sess.scratch(max(batch * rows * n_out, 1) * out_dtype.itemsize)  # the envelope stays on the device for the caller's stage
     env_ptr = sess.scratch(max(batch * rows * n_out, 1) * real.itemsize) if job["detrend"] else None
     ctx.onset_exec(s_ptr, ref_ptr, out_ptr, batch, n_bands, n_frames, real, lag, job["max_size"], code, off_ptr, band_ptr, n_ch, max_ch, job["pad_width"], n_out,
                    item_max_ptr=item_max_ptr, amin=_AMIN, top_db=_TOP_DB, detrend_env_ptr=env_ptr)
+    if stage is not None:
+        return stage(sess, out_ptr, batch * rows, n_out, out_dtype)
     return handle, rows, n_out
 
 
@@ -228,6 +234,15 @@ def _fused(y, sr, n_fft, hop_length, ref, job, kwargs):
         n = int(y.shape[-1])
         return _slow_path(res, 1 + (n + 2 * (n_fft // 2) - n_fft) // int(hop_length), job)
     return res
+
+
+def _strength_then(y, *, sr, hop_length, stage):
+    """``onset_strength(y=y, sr=sr, hop_length=hop_length)`` (every other argument at its default) without downloading the envelope:
+    ``stage(sess, env_ptr, rows, n, dtype) -> (handle, rows, cols)`` runs further device work on the ``[rows][n]`` envelope (one row per
+    clip) and its result comes back as ``(..., rows, cols)`` (``feature.tempogram`` / ``tempo``)."""
+    n_fft = 2048
+    job = dict(lag=1, max_size=1, code=_MEAN, aggregate=np.mean, channels=None, pad_width=1 + n_fft // (2 * hop_length), center=True, detrend=False, stage=stage)
+    return _fused(y, sr, n_fft, hop_length, None, job, {"fmax": 0.5 * sr})
 
 
 def _given(S, ref, job, db):
