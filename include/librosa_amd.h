@@ -322,6 +322,22 @@ int64_t lra_tempogram_work_bytes(int64_t batch, int64_t n_frames, int win_length
 int lra_tempogram_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, int win_length, int center, const void* window, int norm, int mode,
                        const void* logprior, const void* bpms, void* out, void* work, int* nonfinite);
 
+/* ---- beat tracking: librosa.beat.beat_track's dynamic program, librosa/beat.py:510-741 ---------------------------------------------- */
+#define LRA_BEAT_BPM_PER_ROW 0    /* bpm: float64 [batch], one tempo per envelope (:298-301) */
+#define LRA_BEAT_BPM_PER_FRAME 1  /* bpm: float64 [batch][n], a tempo per frame (:598-608, :639) */
+/* Bytes of device scratch `work` that lra_beat_exec needs for these sizes. */
+int64_t lra_beat_work_bytes(int64_t batch, int64_t n, int bpm_mode);
+/* env: [batch][n] onset envelopes of `dtype` (device); bpm: device float64 (see the modes), every value > 0 (:533).  Per row:
+ * x / (std(ddof=1) + tiny) in `dtype` (:567-570), frames_per_beat = round(frame_rate * 60 / bpm) half-even in float64 (:546), the local
+ * score (:576-608; one rounding to `dtype` per term, increasing k), the recurrence in float64 with tightness rounded to float32 (:619-660;
+ * the largest predecessor wins a tie), the last beat (:697-729), the walk along the back-links (:736-741) and the trim with threshold
+ * 0.5 rms of the Hann-smoothed beat scores, or 0 with trim == 0 (:667-694).  out: uint8 [batch][n], 1 = beat.  Rows the reference cannot
+ * handle get no beats: n < 2, a row without a non-zero entry, frames_per_beat outside [2, 2^29].  work: device scratch of
+ * lra_beat_work_bytes bytes.  any_nonzero (host, may be NULL): set to 1 when some entry of env is non-zero (:280) -- reading it waits for
+ * the stream. */
+int lra_beat_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, const void* bpm, int bpm_mode, double frame_rate, double tightness, int trim, void* out,
+                  void* work, int* any_nonzero);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

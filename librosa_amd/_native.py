@@ -97,6 +97,8 @@ SIGNATURES = {
     "lra_maxfilter_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int]),
     "lra_onset_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
                                c_double, c_double, c_void_p, c_int, c_void_p]),
+    "lra_beat_work_bytes": (c_int64, [c_int64, c_int64, c_int]),
+    "lra_beat_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_tempogram_work_bytes": (c_int64, [c_int64, c_int64, c_int, c_int]),
     "lra_tempogram_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_fir_decimate_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int]),
@@ -549,6 +551,17 @@ class Context:
         flag = c_int(0)
         _check(self.lib.lra_tempogram_exec(self.handle, c_void_p(env_ptr), int(batch), int(n), dtype_code(dtype), int(win_length), int(bool(center)), c_void_p(window_ptr), int(norm),
                                            int(mode), c_void_p(logprior_ptr or None), c_void_p(bpms_ptr or None), c_void_p(out_ptr), c_void_p(work_ptr), byref(flag)))
+        return bool(flag.value)
+
+    def beat_work_bytes(self, batch, n, bpm_mode):
+        return int(self.lib.lra_beat_work_bytes(int(batch), int(n), int(bpm_mode)))
+
+    def beat_exec(self, env_ptr, batch, n, dtype, bpm_ptr, bpm_mode, frame_rate, tightness, trim, out_ptr, work_ptr):
+        """The beat tracker on [batch][n] envelopes (``include/librosa_amd.h``: lra_beat_exec).  Returns True when some entry of the envelopes
+        is non-zero (this waits for the stream)."""
+        flag = c_int(0)
+        _check(self.lib.lra_beat_exec(self.handle, c_void_p(env_ptr), int(batch), int(n), dtype_code(dtype), c_void_p(bpm_ptr), int(bpm_mode), float(frame_rate), float(tightness),
+                                      int(bool(trim)), c_void_p(out_ptr), c_void_p(work_ptr), byref(flag)))
         return bool(flag.value)
 
     def fir_decimate_exec(self, x_ptr, out_ptr, batch, n_in, n_out, taps_ptr, n_taps, down, first, div, mul, dtype):

@@ -58,6 +58,43 @@ def fourier_tempo_frequencies(*, sr=22050, win_length=384, hop_length=512):
     return fft_frequencies(sr=sr * 60 / float(hop_length), n_fft=win_length)
 
 
+def frames_to_samples(frames, *, hop_length=512, n_fft=None):
+    """Frame indices -> sample indices (``librosa/core/convert.py:88-129``)."""
+    offset = 0
+    if n_fft is not None:
+        offset = int(n_fft // 2)
+    return (np.asanyarray(frames) * hop_length + offset).astype(int)[()]
+
+
+def samples_to_frames(samples, *, hop_length=512, n_fft=None):
+    """Sample indices -> frame indices, ``floor((samples - n_fft // 2) / hop_length)`` (``librosa/core/convert.py:143-195``)."""
+    offset = 0
+    if n_fft is not None:
+        offset = int(n_fft // 2)
+    samples = np.asanyarray(samples)
+    return np.asarray(np.floor((samples - offset) // hop_length), dtype=int)[()]
+
+
+def frames_to_time(frames, *, sr=22050, hop_length=512, n_fft=None):
+    """Frame indices -> seconds (``librosa/core/convert.py:214-256``)."""
+    return samples_to_time(frames_to_samples(frames, hop_length=hop_length, n_fft=n_fft), sr=sr)
+
+
+def time_to_frames(times, *, sr=22050, hop_length=512, n_fft=None):
+    """Seconds -> frame indices (``librosa/core/convert.py:275-324``)."""
+    return samples_to_frames(time_to_samples(times, sr=sr), hop_length=hop_length, n_fft=n_fft)
+
+
+def time_to_samples(times, *, sr=22050):
+    """Seconds -> sample indices, truncated (``librosa/core/convert.py:333-361``)."""
+    return (np.asanyarray(times) * sr).astype(int)[()]
+
+
+def samples_to_time(samples, *, sr=22050):
+    """Sample indices -> seconds (``librosa/core/convert.py:370-405``)."""
+    return np.asanyarray(samples)[()] / float(sr)
+
+
 def mel_frequencies(n_mels=128, *, fmin=0.0, fmax=11025.0, htk=False):
     lo = hz_to_mel(fmin, htk=htk)
     hi = hz_to_mel(fmax, htk=htk)

@@ -70,23 +70,34 @@ def tempo(*, y=None, sr=22050, onset_envelope=None, tg=None, hop_length=512, sta
     if start_bpm <= 0:
         raise ParameterError("start_bpm must be strictly positive")
     if tg is None:
-        # time_to_frames(ac_size, sr=sr, hop_length=hop_length) (core/convert.py: time_to_samples, samples_to_frames)
-        win_length = int(np.floor((np.asanyarray(ac_size) * sr).astype(int) // hop_length).astype(int))
+        win_length = _ac_frames(ac_size, sr, hop_length)
         device = aggregate is np.mean or aggregate is None
         if not device:
             tg = tempogram(y=y, sr=sr, onset_envelope=onset_envelope, hop_length=hop_length, win_length=win_length)
         else:
-            if win_length < 1:
-                raise ParameterError("win_length must be a positive integer")
-            bpms, logprior = _tables(win_length, hop_length, sr, start_bpm, std_bpm, max_tempo, prior)
-            ac_window = np.ascontiguousarray(filters.get_window("hann", win_length, fftbins=True), dtype=np.float64)
-            job = dict(W=win_length, center=True, window=ac_window, norm=_NORM_INF, mode=_SUM if aggregate is np.mean else _ARGMAX, bpms=bpms, logprior=logprior)
+            job = _tempo_job(win_length, sr, hop_length, start_bpm, std_bpm, max_tempo, prior, _SUM if aggregate is np.mean else _ARGMAX)
             res = _run(y, sr, onset_envelope, hop_length, job)  # (..., 1, 1) or (..., 1, n_frames)
             return res[..., 0, :]
     else:
         win_length = int(tg.shape[-2])
     bpms, logprior = _tables(win_length, hop_length, sr, start_bpm, std_bpm, max_tempo, prior)
     return _score_host(tg, aggregate, bpms, logprior)
+
+
+def _ac_frames(ac_size, sr, hop_length):
+    """time_to_frames(ac_size, sr=sr, hop_length=hop_length) (core/convert.py: time_to_samples, samples_to_frames)."""
+    return int(np.floor((np.asanyarray(ac_size) * sr).astype(int) // hop_length).astype(int))
+
+
+def _tempo_job(win_length, sr, hop_length, start_bpm, std_bpm, max_tempo, prior, mode):
+    """The tempogram kernel's job for a tempo estimate (``tempo`` and ``beat.beat_track`` share it): the tables, the Hann window, the mode."""
+    if start_bpm <= 0:
+        raise ParameterError("start_bpm must be strictly positive")
+    if win_length < 1:
+        raise ParameterError("win_length must be a positive integer")
+    bpms, logprior = _tables(win_length, hop_length, sr, start_bpm, std_bpm, max_tempo, prior)
+    ac_window = np.ascontiguousarray(filters.get_window("hann", win_length, fftbins=True), dtype=np.float64)
+    return dict(W=win_length, center=True, window=ac_window, norm=_NORM_INF, mode=mode, bpms=bpms, logprior=logprior)
 
 
 # ---- host tables and the slow path ------------------------------------------------------------------------------------------------------

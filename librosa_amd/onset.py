@@ -236,12 +236,14 @@ def _fused(y, sr, n_fft, hop_length, ref, job, kwargs):
     return res
 
 
-def _strength_then(y, *, sr, hop_length, stage):
-    """``onset_strength(y=y, sr=sr, hop_length=hop_length)`` (every other argument at its default) without downloading the envelope:
-    ``stage(sess, env_ptr, rows, n, dtype) -> (handle, rows, cols)`` runs further device work on the ``[rows][n]`` envelope (one row per
-    clip) and its result comes back as ``(..., rows, cols)`` (``feature.tempogram`` / ``tempo``)."""
+def _strength_then(y, *, sr, hop_length, stage, aggregate=np.mean):
+    """``onset_strength(y=y, sr=sr, hop_length=hop_length, aggregate=aggregate)`` (every other argument at its default; ``aggregate`` one of
+    the device aggregates) without downloading the envelope: ``stage(sess, env_ptr, rows, n, dtype) -> (handle, rows, cols)`` runs further
+    device work on the ``[rows][n]`` envelope (one row per clip) and its result comes back as ``(..., rows, cols)`` (``feature.tempogram`` /
+    ``tempo``; ``beat.beat_track`` with ``np.median``)."""
     n_fft = 2048
-    job = dict(lag=1, max_size=1, code=_MEAN, aggregate=np.mean, channels=None, pad_width=1 + n_fft // (2 * hop_length), center=True, detrend=False, stage=stage)
+    code = next(c for f, c in _DEVICE_AGGREGATES if aggregate is f)
+    job = dict(lag=1, max_size=1, code=code, aggregate=aggregate, channels=None, pad_width=1 + n_fft // (2 * hop_length), center=True, detrend=False, stage=stage)
     return _fused(y, sr, n_fft, hop_length, None, job, {"fmax": 0.5 * sr})
 
 
