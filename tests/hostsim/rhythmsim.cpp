@@ -55,10 +55,10 @@ alignas(16) static unsigned char g_postsim_dyn_lds[160 * 1024];  // the dynamic 
 
 #include "../../librosa_amd/csrc/lra_rhythm.h"
 
-// transform lengths instantiated here (a subset of LRA_MIXED_SIZES, to keep the simulator's compile short); sim_transform_length is
-// lra_rhythm_launch.h's transform_length over the full list, -1 where its choice is not instantiated here
-#define LRA_RHYTHM_SIM_SIZES(X) X(160) X(320) X(720) X(800) X(882) X(1440) X(1600)
+// transform lengths instantiated here: every size of LRA_MIXED_SIZES, as the device library (tests/test_rhythm_edges_host.py runs them all);
+// sim_transform_length is lra_rhythm_launch.h's transform_length over the full list, -1 where its choice is not instantiated here
 #define LRA_MIXED_SIZES(X) X(160) X(200) X(240) X(320) X(400) X(480) X(600) X(640) X(720) X(800) X(882) X(960) X(1000) X(1200) X(1280) X(1440) X(1600) X(1764) X(1920) X(2000) X(2400) X(2646) X(3200) X(3528) X(4800)
+#define LRA_RHYTHM_SIM_SIZES(X) LRA_MIXED_SIZES(X)
 static int sim_transform_length(int W) {
     int best = 0;
 #define LRA_RHYTHM_CASE(N) \
