@@ -78,9 +78,10 @@ def mel_band(B):
     return c0, ln, off, np.ascontiguousarray(val)
 
 
-def stft(y, n_fft, hop, win, center=True, pad_mode="constant", mode=0, iters_per_wg=1, power=2.0, mel_basis=None, variant=0, row_pad=0):
+def stft(y, n_fft, hop, win, center=True, pad_mode="constant", mode=0, iters_per_wg=1, power=2.0, mel_basis=None, variant=0, row_pad=0, decline_ok=False):
     """y: (batch, n) f32/f64.  mode 0 -> complex (batch, T, M+1); 1 -> power; 2 / 3 / 4 -> mel (batch, n_mels, T)
     through the generic banded path / the two-slope path / its run-ordered form.
+    decline_ok: mode 3 answers (None, dict(unavailable=..)) like mode 4 where its table form does not apply to the bank, instead of failing.
     row_pad (modes 0 / 1): rows `M + 1 + row_pad` elements apart (StftArgs::row_pitch); the whole padded buffer comes back, NaN where nothing was stored."""
     y = np.ascontiguousarray(y)
     assert y.ndim == 2
@@ -115,7 +116,7 @@ def stft(y, n_fft, hop, win, center=True, pad_mode="constant", mode=0, iters_per
             ctypes.c_int(hop), ctypes.c_int(int(center)), ctypes.c_int(PAD_MODES[pad_mode]), _p(win), ctypes.c_int(iters_per_wg), _p(out),
             ctypes.c_int(pm), ctypes.c_double(power), _p(c0), _p(ln), _p(off), _p(val), ctypes.c_int(n_mels), ctypes.c_int(variant), _p(dense), _p(diag))
     assert rc == 0, "unsupported n_fft for the pow2 kernels"
-    if mode == 4 and diag[7] != 0:
+    if (mode == 4 or (mode == 3 and decline_ok)) and diag[7] != 0:
         return None, dict(unavailable=int(diag[7]))  # run-ordered form not applicable to this configuration (the library falls back too)
     assert diag[7] == 0, "two-slope mel form not applicable"
     return out, dict(races=int(diag[0]), uninit=int(diag[1]), NT=int(diag[2]), FPB=int(diag[3]), P=int(diag[4]), lds=int(diag[5]), wave_sync=int(diag[6]), ring_aligned=int(diag[8]), max_pieces=int(diag[9]), v2=int(diag[10]), mel_many=int(diag[11]))
