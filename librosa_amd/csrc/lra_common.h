@@ -81,6 +81,13 @@ template <int S1L, int S1H, int N0L, int N0H, int N1L, int N1H> __device__ __for
         : "=v"(r) : "v"(a), "v"(b), "n"(S1L), "n"(S1H), "n"(N0L), "n"(N1L), "n"(N0H), "n"(N1H));
     return r;
 }
+// r.lo = (+-a[S0L]) + (+-b[S1L]);  r.hi = (+-a[S0H]) + (+-b[S1H])      (either half of either operand on either side)
+template <int S0L, int S0H, int S1L, int S1H, int N0L, int N0H, int N1L, int N1H> __device__ __forceinline__ f2 add_sel(f2 a, f2 b) {
+    f2 r;
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[%3,%4] op_sel_hi:[%5,%6] neg_lo:[%7,%8] neg_hi:[%9,%10]"
+        : "=v"(r) : "v"(a), "v"(b), "n"(S0L), "n"(S1L), "n"(S0H), "n"(S1H), "n"(N0L), "n"(N1L), "n"(N0H), "n"(N1H));
+    return r;
+}
 // r.lo = a[S0L] * b[S1L];  r.hi = a[S0H] * b[S1H]
 template <int S0L, int S0H, int S1L, int S1H> __device__ __forceinline__ f2 mul(f2 a, f2 b) {
     f2 r;
@@ -358,6 +365,9 @@ template <class V> inline void lds_st(Lds l, int byte_off, V v) {
     std::memcpy(s.mem.data() + l.base + byte_off, &v, sizeof(V));
 }
 inline Lds lds_sub(Lds l, int byte_off) { Lds r; r.base = l.base + byte_off; return r; }
+// byte address in a view, as a value that address arithmetic may work on (lds_st_addr stores through it).  Here: the offset itself.
+inline int lds_addr(Lds, int byte_off) { return byte_off; }
+template <class V> inline void lds_st_addr(Lds l, int addr, V v) { lds_st<V>(l, addr, v); }
 
 #define LRA_LAUNDER(p) ((void)0)
 #define LRA_ATOMIC_OR(ptr, v) (*(ptr) |= (v))
@@ -405,6 +415,11 @@ template <class V> LRA_HD V lds_ld(Lds l, int byte_off) {
 }
 template <class V> LRA_HD void lds_st(Lds l, int byte_off, V v) { *reinterpret_cast<V*>(l.base + byte_off) = v; }
 LRA_HD Lds lds_sub(Lds l, int byte_off) { Lds r; r.base = l.base + byte_off; return r; }
+// byte address in a view, as a value that address arithmetic may work on (lds_st_addr stores through it).  On the device: the absolute
+// 32-bit LDS address, so that one add of the view's base serves every address derived from it by XOR or by constant steps (the steps go
+// into the instruction's offset field).  XOR of bit b commutes with the base where the view starts on a multiple of 2^(b + 1) bytes.
+__device__ __forceinline__ int lds_addr(Lds l, int byte_off) { return (int)(unsigned int)(size_t)(__attribute__((address_space(3))) char*)(l.base + byte_off); }
+template <class V> __device__ __forceinline__ void lds_st_addr(Lds, int addr, V v) { *(__attribute__((address_space(3))) V*)(size_t)(unsigned int)addr = v; }
 
 // makes the compiler forget what it knows about a (uniform) pointer: loads through it cannot be
 // hoisted out of the enclosing loop

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(Cfg::NT, (Cfg::NT > 256 ? 1 : (Cfg::TF == 64 && HD 
 // Producer / consumer form of the fused mel kernel (lra_kernels_pc.h): 192-thread workgroups [P, P, C], three waves per SIMD.
 template <class Cfg, int HD, int PM>
 __global__ __launch_bounds__(lra::PcLayout<Cfg>::NT, 3) void stft_pc_kernel(lra::StftArgs<typename Cfg::real> a, const typename Cfg::real* __restrict__ y, void* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char lra_smem[];
+    extern __shared__ __attribute__((aligned(32))) char lra_smem[];  // (32: v2_pw_addr_xor flips bit 4 of absolute LDS addresses)
     lra::Lds lds;
     lds.base = lra_smem;
     a.y = y;

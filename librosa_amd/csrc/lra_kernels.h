@@ -603,6 +603,25 @@ template <class T> LRA_HD void split_pair(cx<T> zk, cx<T> zm, cx<T> w, cx<T>& xk
     xm = conj_sub(A, B);
 }
 
+// (|X[k]|^2, |X[M-k]|^2) of the same pair -- the power form of the run-ordered mel epilogue, shared by stft2_kernel<OUT_MELR> and the
+// producer / consumer kernel.  The last two additions of split_pair deliver the pair transposed, (re X[k], re X[M-k]) and
+// (im X[k], im X[M-k]), and both squared moduli then come out of ONE packed multiply and ONE packed FMA (|X|^2 per value as
+// spec_power spells it is a packed multiply and a scalar add per value).  The FMA rounds once: re^2 is rounded, im^2 + re^2 is not
+// rounded in between; the plain body below says the same with std::fma.
+template <class T> LRA_HD cx<T> split_pair_pow2(cx<T> zk, cx<T> zm, cx<T> w) {
+    const cx<T> A = add_conj(zk, zm);
+    const cx<T> B = cmul2_mi(sub_conj(zk, zm), w);
+#ifdef LRA_PK_ASM
+    if constexpr (sizeof(T) == 4) {
+        const pk::f2 re = pk::add_sel<0, 0, 0, 0, 0, 0, 0, 1>(pk::v(A), pk::v(B));  // (A.x + B.x, A.x - B.x)
+        const pk::f2 im = pk::add_sel<1, 1, 1, 1, 0, 1, 0, 0>(pk::v(A), pk::v(B));  // (A.y + B.y, B.y - A.y)
+        return pk::c(pk::fma<0, 1, 0, 1, 0, 0>(im, im, pk::mul<0, 1, 0, 1>(re, re)));
+    }
+#endif
+    const T rk = A.x + B.x, rm = A.x - B.x, ik = A.y + B.y, im = B.y - A.y;
+    return mk<T>(std::fma(ik, ik, rk * rk), std::fma(im, im, rm * rm));
+}
+
 // ---- phase: split + epilogue store (complex / power) or power -> LDS (mel) --------------------
 template <class Cfg, int MODE, int PM> LRA_HD void stft_split_store(const StftArgs<typename Cfg::real>& a, int clip, int frame, bool valid, int tf,
                                                             FftRegs<Cfg>& rg, Lds fr, Lds sh) {

@@ -374,6 +374,32 @@ template <bool SWZ> LRA_HD int v2_pw_index_t(int k) {
 template <class Cfg> LRA_HD int v2_pw_index(int k) { return v2_pw_index_t<v2_pw_swz<Cfg>()>(k); }
 template <class Cfg> constexpr int v2_pw_bytes() { return (v2_pw_swz<Cfg>() ? Cfg::M + 8 : (Cfg::M >> 3) * 12 + 4) * (int)sizeof(typename Cfg::real); }
 
+// Store addresses (lds_addr values) of the swizzled power row for v2_last_split_store's sixteen stores, without v2_pw_index per family.
+// In bytes the swizzle is: 4 k with bit 4 flipped where bit 7 of k is set, and a step of one pair slot (s = 128 bins) flips bit 7 of k.  So
+//   bin k = tf' + q s          sits at   (4 tf' ^ 16 par) + 4 s q,                      par = q & 1      (tf' < s / 2, or lane 0's tfh: bit 7 of tf' clear, 4 tf' a multiple of 32)
+//   bin M - k                  sits at   ((4 (M - tf')) ^ 16 (1 - par)) - 4 s q                           (bit 7 of M - tf' is set: 1 <= tf' < s / 2, and lane 0's tfh)
+// except lane 0's own family (tf' = 0: bins M - q s, bit 7 of M clear), where the parities swap.  All steps are multiples of 32 bytes, so the
+// XOR may be applied to an address that already holds the view's base (a multiple of 32 bytes too: static_assert in stft_pc_block) and the
+// steps go into the stores' offset fields.  The mirrored families count up from their LOWEST address (slot r - 1) so that every step is positive:
+//   ak[f][par] + (par s + 2 s (q >> 1)) 4           is bin k's address,       am[f][par] + ((1 - par) s + 2 s (r / 2 - 1 - (q >> 1))) 4      bin M - k's
+// (f = 0: tf' = tf, pair slots q < r / 2; f = 1: tf' = tfh, the others).  Two subtractions, a select and five XORs instead of a shift, a
+// three-input bit operation and a scaled add for each of eight address registers.
+template <class Cfg> LRA_HD void v2_pw_addr_xor(Lds stage, int tf, int tfh, bool l0, int (&ak)[2][2], int (&am)[2][2]) {
+    using T = typename Cfg::real;
+    constexpr int p = Cfg::P - 1, r = 1 << Cfg::logr(p), s = 2 * Cfg::TF, M = Cfg::M, SZ = (int)sizeof(T);
+    static_assert(v2_pw_swz<Cfg>() && SZ == 4 && s == 128, "bit 4 of the byte address swaps the halves of a run, bit 7 of the bin selects");
+    constexpr int LOW = M - (r - 1) * s;  // lowest bin of a mirrored family is LOW - tf'
+    ak[0][0] = lds_addr(stage, tf * SZ);
+    ak[1][0] = lds_addr(stage, tfh * SZ);
+    am[1][1] = lds_addr(stage, (LOW - tfh) * SZ);
+    LRA_UNROLL
+    for (int f = 0; f < 2; ++f) ak[f][1] = ak[f][0] ^ 16;
+    am[1][0] = am[1][1] ^ 16;
+    // lane 0's own family: bins M - q s.  Even slots (par 0) are un-swizzled there, odd ones swizzled
+    am[0][0] = l0 ? lds_addr(stage, LOW * SZ) : am[1][0];
+    am[0][1] = am[0][0] ^ 16;
+}
+
 // phase: last-pass butterflies, Hermitian split in registers, epilogue (complex spectrum or |X|^power) to HBM
 template <class Cfg, int HD, int MODE, int PM, bool STAGED, bool PIN = true>
 LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip, int frame, bool valid, int tf, Regs2<Cfg, HD>& rg, Lds stage) {
@@ -396,7 +422,14 @@ LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
     // (4 VALU instructions each) rather than keep four values live
     // ([family][parity of the pair slot]: the swizzled row is linear over steps of TWO slots (256 bins), so each family has two bases)
     int pwk[2][2] = {{0, 0}, {0, 0}}, pwm[2][2] = {{0, 0}, {0, 0}};
-    if (MODE == OUT_MELR) {
+    // PIN = false on the swizzled row (the producer / consumer kernel): the sixteen addresses come from the view's base by two
+    // subtractions, a select and XORs of bit 4, see v2_pw_addr_xor
+    constexpr bool AXOR = MODE == OUT_MELR && !PIN && v2_pw_swz<Cfg>();
+    // |X|^2: both values of a pair slot from one packed multiply and one packed FMA (split_pair_pow2)
+    constexpr bool POW2 = MODE == OUT_MELR && PM == POW_TWO;
+    int ak[2][2] = {{0, 0}, {0, 0}}, am[2][2] = {{0, 0}, {0, 0}};
+    if constexpr (AXOR) v2_pw_addr_xor<Cfg>(stage, tf, tfh, l0, ak, am);
+    if (MODE == OUT_MELR && !AXOR) {
         LRA_UNROLL
         for (int par = 0; par < 2; ++par) {
             pwk[0][par] = v2_pw_index<Cfg>(tf + par * s) * (int)sizeof(T);
@@ -416,25 +449,36 @@ LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
         if (q == 0) zm = B[r - 1];
         else if (q < r / 2) zm = sel_mask(l0m, l0, A[r - q], B[r - 1 - q]);
         else zm = sel_mask(l0m, l0, B[3 * r / 2 - 1 - q], B[r - 1 - q]);
-        C xk, xm;
-        split_pair<T>(zk, zm, rg.twr[q], xk, xm);
+        C xk = mk<T>((T)0, (T)0), xm = xk;
+        C pp = xk;  // POW2: (|X[k]|^2, |X[M-k]|^2)
+        if constexpr (POW2) pp = split_pair_pow2<T>(zk, zm, rg.twr[q]);
+        else split_pair<T>(zk, zm, rg.twr[q], xk, xm);
         if (q == 0) {
             const C z0 = A[0];  // Z is pre-halved (see split_pair)
             const C dc = mk<T>((T)2 * (z0.x + z0.y), (T)0), ny = mk<T>((T)2 * (z0.x - z0.y), (T)0);
-            xk = sel_mask(l0m, l0, dc, xk);
-            xm = sel_mask(l0m, l0, ny, xm);
+            if constexpr (POW2) {
+                // (two real values: their squares are selected, not two complex numbers)
+                pp = mk<T>(sel_mask(l0m, l0, dc.x * dc.x, pp.x), sel_mask(l0m, l0, ny.x * ny.x, pp.y));
+            } else {
+                xk = sel_mask(l0m, l0, dc, xk);
+                xm = sel_mask(l0m, l0, ny, xm);
+            }
             if (LRA_UNLIKELY(l0 && valid && a.nonfinite_flag && !(std::fabs(dc.x) <= std::numeric_limits<T>::max()))) LRA_ATOMIC_OR(a.nonfinite_flag, 1u);
         }
         const int k = (q < r / 2 ? tf : tfh) + q * s;
         if (MODE == OUT_MELR) {
+            const T vk = POW2 ? pp.x : spec_power<T, PM>(xk, a.power), vm = POW2 ? pp.y : spec_power<T, PM>(xm, a.power);
             // power row -> LDS (the frame area is free: every Z is in registers), bin k at float (k / 8) 12 + k % 8: runs of 8
             // bins 48 bytes apart, so that the 16-byte run reads of v2_mel_runs_read hit disjoint banks.  Per-thread bases + immediates.
-            if (v2_pw_swz<Cfg>()) {
-                lds_st<T>(stage, pwk[q < r / 2 ? 0 : 1][q & 1] + (q >> 1) * 2 * s * (int)sizeof(T), spec_power<T, PM>(xk, a.power));
-                lds_st<T>(stage, pwm[q < r / 2 ? 0 : 1][q & 1] - (q >> 1) * 2 * s * (int)sizeof(T), spec_power<T, PM>(xm, a.power));
+            if constexpr (AXOR) {
+                lds_st_addr<T>(stage, ak[q < r / 2 ? 0 : 1][q & 1] + ((q & 1) * s + (q >> 1) * 2 * s) * (int)sizeof(T), vk);
+                lds_st_addr<T>(stage, am[q < r / 2 ? 0 : 1][q & 1] + ((1 - (q & 1)) * s + (r / 2 - 1 - (q >> 1)) * 2 * s) * (int)sizeof(T), vm);
+            } else if (v2_pw_swz<Cfg>()) {
+                lds_st<T>(stage, pwk[q < r / 2 ? 0 : 1][q & 1] + (q >> 1) * 2 * s * (int)sizeof(T), vk);
+                lds_st<T>(stage, pwm[q < r / 2 ? 0 : 1][q & 1] - (q >> 1) * 2 * s * (int)sizeof(T), vm);
             } else {
-                lds_st<T>(stage, pwk[q < r / 2 ? 0 : 1][0] + 24 * q * (s / 16) * (int)sizeof(T), spec_power<T, PM>(xk, a.power));
-                lds_st<T>(stage, pwm[q < r / 2 ? 0 : 1][0] - 24 * q * (s / 16) * (int)sizeof(T), spec_power<T, PM>(xm, a.power));
+                lds_st<T>(stage, pwk[q < r / 2 ? 0 : 1][0] + 24 * q * (s / 16) * (int)sizeof(T), vk);
+                lds_st<T>(stage, pwm[q < r / 2 ? 0 : 1][0] - 24 * q * (s / 16) * (int)sizeof(T), vm);
             }
         } else if (MODE == OUT_COMPLEX && STAGED) {
             // the row goes to LDS in bin order (the frame area is free: every Z is in registers), shifted so that LDS and
@@ -736,6 +780,9 @@ LRA_HD void v3_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
     // pieces 2 and 3 carry X[2 s] = xmid and X[3 s] / X[s] = slot 1's results -- bins s, 2 s, 3 s are written twice (ascending and mirrored piece) from
     // the SAME register.  Slot 1 goes first because pieces 3 need it.
     C x1k = mk<T>((T)0, (T)0), x1m = x1k;
+    // |X|^2 into the power row: both values of a pair slot from one packed multiply and one packed FMA (split_pair_pow2), and thread 0's
+    // substitutions select real values instead of complex ones
+    constexpr bool POW2 = MODE == OUT_MELR && PM == POW_TWO;
     LRA_UNROLL
     for (int jo = 0; jo < 4; ++jo) {
         const int j = jo == 0 ? 1 : (jo == 1 ? 0 : jo);  // 1, 0, 2, 3
@@ -748,11 +795,34 @@ LRA_HD void v3_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
             else if (j == 2) wO = cmul_mi(t);                                               // e^(-i pi / 2) = -i
             else { const C u = sub_mi(t, t); wO = mk<T>(-h * u.x, -h * u.y); }              // e^(-3 i pi / 4) = -h (1 + i)
         }
-        split_pair<T>(O[j], Om[3 - j], wO, xkO, xmO);
         C zk = E[j], zm = Em[3 - j];
         if (j == 1) zm = sel_mask(l0m, l0, E[3], Em[2]);
         if (j == 2) { zk = sel_mask(l0m, l0, Em[0], E[2]); zm = sel_mask(l0m, l0, Em[3], Em[1]); }
         if (j == 3) { zk = sel_mask(l0m, l0, Em[1], E[3]); zm = sel_mask(l0m, l0, Em[2], Em[0]); }
+        if constexpr (POW2) {
+            static_assert(v2_pw_swz<Cfg>(), "swizzled power row");
+            const C pO = split_pair_pow2<T>(O[j], Om[3 - j], wO);  // (|X|^2 of the O slot's bin, of its mirror)
+            C pE = split_pair_pow2<T>(zk, zm, rg.twr[j]);
+            if (j == 0) {
+                const C z0 = E[0];  // Z is pre-halved (see split_pair)
+                const T dc = (T)2 * (z0.x + z0.y), ny = (T)2 * (z0.x - z0.y);
+                pE = mk<T>(sel_mask(l0m, l0, dc * dc, pE.x), sel_mask(l0m, l0, ny * ny, pE.y));
+                if (LRA_UNLIKELY(l0 && valid && a.nonfinite_flag && !(std::fabs(dc) <= std::numeric_limits<T>::max()))) LRA_ATOMIC_OR(a.nonfinite_flag, 1u);
+            }
+            if (j == 1) x1k = pE;  // (as powers: x1k = (|X[s]|^2, |X[3 s]|^2) of thread 0)
+            T asc = pE.x, mir = pE.y;  // the E halves of the two pieces
+            if (j == 2) { const T pmid = spec_power<T, PM>(xmid, a.power); asc = sel_mask(l0m, l0, pmid, pE.x); mir = sel_mask(l0m, l0, pmid, pE.y); }
+            if (j == 3) { asc = sel_mask(l0m, l0, x1k.y, pE.x); mir = sel_mask(l0m, l0, x1k.x, pE.y); }
+            lds_st<C>(stage, ia + j * s * (int)sizeof(T), mk<T>(asc, pO.x));
+            lds_st<T>(stage, im1 - j * s * (int)sizeof(T), pO.y);
+            lds_st<T>(stage, im0 - j * s * (int)sizeof(T), mir);
+            if (j >= 2 && l0) {
+                lds_st<T>(stage, v2_pw_index<Cfg>(s / 2 + (j - 2) * s) * (int)sizeof(T), pE.x);
+                lds_st<T>(stage, v2_pw_index<Cfg>(M - s / 2 - (j - 2) * s) * (int)sizeof(T), pE.y);
+            }
+            continue;
+        }
+        split_pair<T>(O[j], Om[3 - j], wO, xkO, xmO);
         split_pair<T>(zk, zm, rg.twr[j], xkE, xmE);
         if (j == 0) {
             const C z0 = E[0];  // Z is pre-halved (see split_pair)

@@ -455,6 +455,9 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
     }
 #else
     // ---- device: the three waves run their own loops
+    // (the lane index is phase_tid() & (TF - 1): behind the opaque move hipcc no longer knows that the thread index is not negative, and
+    // `% TF` is then the five-instruction signed remainder, once per phase)
+    static_assert((TF & (TF - 1)) == 0 && L::pw_off(0) % 32 == 0 && L::PW % 32 == 0, "lane mask; power rows start on 32 bytes (v2_pw_addr_xor)");
     if (threadIdx.x < 2 * NP) pc_flag_store(lds, L::flags_off() + 4 * (int)threadIdx.x, 0);
     phase_sync<false>();  // the only workgroup barrier of the kernel
     const int wave = LRA_UNIFORM((int)(threadIdx.x / TF));
@@ -462,7 +465,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
         RG rg;
         const Lds fr = lds_sub(lds, L::frame_off(wave)), pwr = lds_sub(lds, L::pw_off(wave));
         {
-            const int tf = phase_tid() % TF;
+            const int tf = (phase_tid() & (TF - 1));
             pc_producer_prologue<Cfg, HD>(a, clip, f_first + wave * iters, tf, rg);
         }
         pc_fence();
@@ -470,15 +473,15 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
             const int frame = f_first + wave * iters + it;
             v2_setprio<LRA_PC_PRIO_PA>();
             {
-                const int tf = phase_tid() % TF;
+                const int tf = (phase_tid() & (TF - 1));
                 pc_producer_pass0<Cfg, HD>(a, clip, frame, it, it + 1 < iters, tf, rg, fr);
             }
             pc_fence();
 #define LRA_PC_MID(p)                                                                                    \
             if (Cfg::P - 1 > p) {                                                                        \
-                { const int tf = phase_tid() % TF; pass_read<Cfg, (p < Cfg::P ? p : 0)>(rg.v, fr, tf); } \
+                { const int tf = (phase_tid() & (TF - 1)); pass_read<Cfg, (p < Cfg::P ? p : 0)>(rg.v, fr, tf); } \
                 pc_fence();                                                                              \
-                { const int tf = phase_tid() % TF; pc_mid_dft_write<Cfg, (p < Cfg::P ? p : 0)>(rg.v, rg.treg, fr, tf); } \
+                { const int tf = (phase_tid() & (TF - 1)); pc_mid_dft_write<Cfg, (p < Cfg::P ? p : 0)>(rg.v, rg.treg, fr, tf); } \
                 pc_fence();                                                                              \
             }
             LRA_PC_MID(1)
@@ -486,7 +489,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
 #undef LRA_PC_MID
             int taken;
             {
-                const int tf = phase_tid() % TF;
+                const int tf = (phase_tid() & (TF - 1));
                 pc_last_read<Cfg, HD>(rg, fr, tf);
                 taken = pc_flag_load(lds, L::consumed_off(wave));  // rides on the same wait as the last pass's inputs
             }
@@ -494,11 +497,11 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
             v2_setprio<LRA_PC_PRIO_PS>();
             if (LRA_UNLIKELY(LRA_UNIFORM(taken) < it)) pc_wait(lds, L::consumed_off(wave), it, a.nonfinite_flag);  // row it - 1 still unread (it was handed over a whole frame ago)
             {
-                const int tf = phase_tid() % TF;
+                const int tf = (phase_tid() & (TF - 1));
                 pc_last_power_row<Cfg, HD, PM>(a, clip, frame, tf, rg, pwr);
             }
             pc_fence();
-            if (phase_tid() % TF == 0) pc_flag_store(lds, L::ready_off(wave), it + 1);  // behind the row's writes in this wave's DS queue
+            if ((phase_tid() & (TF - 1)) == 0) pc_flag_store(lds, L::ready_off(wave), it + 1);  // behind the row's writes in this wave's DS queue
             pc_fence();
         }
     } else {
