@@ -338,6 +338,29 @@ int64_t lra_beat_work_bytes(int64_t batch, int64_t n, int bpm_mode);
 int lra_beat_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, const void* bpm, int bpm_mode, double frame_rate, double tightness, int trim, void* out,
                   void* work, int* any_nonzero);
 
+/* ---- peak picking and onset backtracking: librosa.util.peak_pick (util/utils.py:1183-1496), onset_detect's normalisation (onset.py:164-176),
+ * onset_backtrack's preceding minimum (onset.py:430-441) -------------------------------------------------------------------------------- */
+#define LRA_PEAK_GREEDY 0    /* the earliest frame first (:1188-1217) */
+#define LRA_PEAK_DP_COUNT 1  /* the most peaks (:1225-1281, count) */
+#define LRA_PEAK_DP_VALUE 2  /* the largest sum of peak values */
+#define LRA_PEAK_ANY_NONZERO 1  /* status bit 0: some entry is non-zero */
+#define LRA_PEAK_ALL_FINITE 2   /* status bit 1: every entry is finite */
+/* Bytes of device scratch `work` that lra_peak_pick_exec needs for these sizes. */
+int64_t lra_peak_pick_work_bytes(int64_t batch, int64_t n, int method);
+/* x: [batch][n] rows of `dtype` (device).  normalize != 0: per row x - min, then / (max of that + tiny), each one rounding in `dtype` (the
+ * bits NumPy gives).  A frame is a candidate when x[i] == max(x[i - pre_max : i + post_max]) (a NaN in the window: never for GREEDY, always
+ * for the DP methods, as the reference's comparisons) and x[i] >= mean(x[i - pre_avg : i + post_avg]) + delta, the mean and the comparison in
+ * float64 (the reference's mean is rounded to `dtype`: the two agree wherever the difference is not within that rounding).  GREEDY: the
+ * earliest candidate, then the earliest more than `wait` frames later, and so on.  DP_*: the reference's backward recurrence in float64 and
+ * the walk along its pointers.  Windows and `wait` beyond n count as n.  out: uint8 [batch][n], 1 = peak.  norm_out (may be NULL): receives
+ * the normalised rows (a copy of x with normalize == 0).  work: device scratch of lra_peak_pick_work_bytes bytes.  status (host, may be
+ * NULL): LRA_PEAK_ANY_NONZERO | LRA_PEAK_ALL_FINITE over all normalised rows (onset.py:176) -- reading it waits for the stream. */
+int lra_peak_pick_exec(lra_ctx* ctx, const void* x, int64_t batch, int64_t n, int dtype, int normalize, int64_t pre_max, int64_t post_max, int64_t pre_avg, int64_t post_avg,
+                       double delta, int64_t wait, int method, void* out, void* norm_out, void* work, int* status);
+/* energy: [batch][m] rows of `dtype` (device).  out: int32 [batch][m], out[i] = the largest j <= i with j == 0, or with 1 <= j <= m - 2,
+ * e[j] <= e[j - 1] and e[j] < e[j + 1]: onset_backtrack(events, energy) is out[min(events, m - 1)]. */
+int lra_prev_minimum_exec(lra_ctx* ctx, const void* energy, int64_t batch, int64_t m, int dtype, void* out);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

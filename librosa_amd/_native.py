@@ -99,6 +99,10 @@ SIGNATURES = {
                                c_double, c_double, c_void_p, c_int, c_void_p]),
     "lra_beat_work_bytes": (c_int64, [c_int64, c_int64, c_int]),
     "lra_beat_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_double, c_double, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "lra_peak_pick_work_bytes": (c_int64, [c_int64, c_int64, c_int]),
+    "lra_peak_pick_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                   POINTER(c_int)]),
+    "lra_prev_minimum_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "lra_tempogram_work_bytes": (c_int64, [c_int64, c_int64, c_int, c_int]),
     "lra_tempogram_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_fir_decimate_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int]),
@@ -563,6 +567,23 @@ class Context:
         _check(self.lib.lra_beat_exec(self.handle, c_void_p(env_ptr), int(batch), int(n), dtype_code(dtype), c_void_p(bpm_ptr), int(bpm_mode), float(frame_rate), float(tightness),
                                       int(bool(trim)), c_void_p(out_ptr), c_void_p(work_ptr), byref(flag)))
         return bool(flag.value)
+
+    def peak_pick_work_bytes(self, batch, n, method):
+        return int(self.lib.lra_peak_pick_work_bytes(int(batch), int(n), int(method)))
+
+    def peak_pick_exec(self, x_ptr, batch, n, dtype, normalize, pre_max, post_max, pre_avg, post_avg, delta, wait, method, out_ptr, norm_ptr, work_ptr, status=True):
+        """The peak picker on [batch][n] rows (``include/librosa_amd.h``: lra_peak_pick_exec).  Returns (some entry non-zero, every entry finite)
+        of the normalised rows (this waits for the stream), or (None, None) with ``status=False`` (nothing is read back)."""
+        flag = c_int(0)
+        big = 2**62  # (a window or a dead time beyond the row counts as the row's length)
+        _check(self.lib.lra_peak_pick_exec(self.handle, c_void_p(x_ptr), int(batch), int(n), dtype_code(dtype), int(bool(normalize)), min(int(pre_max), big), min(int(post_max), big),
+                                           min(int(pre_avg), big), min(int(post_avg), big), float(delta), min(int(wait), big), int(method), c_void_p(out_ptr),
+                                           c_void_p(norm_ptr or None), c_void_p(work_ptr), byref(flag) if status else None))
+        return (bool(flag.value & 1), bool(flag.value & 2)) if status else (None, None)
+
+    def prev_minimum_exec(self, energy_ptr, batch, m, dtype, out_ptr):
+        """The preceding-minimum rows of [batch][m] energy rows (lra_prev_minimum_exec)."""
+        _check(self.lib.lra_prev_minimum_exec(self.handle, c_void_p(energy_ptr), int(batch), int(m), dtype_code(dtype), c_void_p(out_ptr)))
 
     def fir_decimate_exec(self, x_ptr, out_ptr, batch, n_in, n_out, taps_ptr, n_taps, down, first, div, mul, dtype):
         _check(self.lib.lra_fir_decimate_exec(self.handle, c_void_p(x_ptr), c_void_p(out_ptr), batch, n_in, n_out, c_void_p(taps_ptr), int(n_taps), int(down), int(first), float(div),

@@ -9,19 +9,25 @@ and returns float64, as the reference does.  With ``S`` given (or another ``feat
 spectrogram.  ``np.mean`` / ``np.sum`` / ``np.max`` / ``np.min`` / ``np.median`` and ``aggregate=False`` run on the device; any other
 aggregate callable is a slow path: the device computes the rectified per-band flux, the callable is applied on the host exactly as
 ``util.sync`` applies it, and the padding / trim / detrend run on the device again.  Device tensors in give device tensors out.
+
+``onset_detect`` (``librosa/onset.py:31-214``) picks peaks of that envelope with ``csrc/lra_peaks.h``.  From ``y`` the envelope never leaves
+the device: the normalisation, the candidate flags and the selection run as a stage behind the flux kernel, and only the ``uint8`` onset row
+comes back (with ``backtrack=True`` also the ``int32`` row of preceding minima, ``onset_backtrack``'s table, ``:370-441``).
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _arrays, filters
+from .core import convert as _convert
 from .core import spectrum as _spectrum
 from .feature import spectral as _spectral
+from .util import peaks as _peaks
 from .util import utils as util
 from .util.exceptions import ParameterError
 from .util.utils import is_torch_tensor
 
-__all__ = ["onset_strength", "onset_strength_multi"]
+__all__ = ["onset_detect", "onset_strength", "onset_strength_multi", "onset_backtrack"]
 
 # aggregation codes of lra_onset_exec (include/librosa_amd.h)
 _NONE, _MEAN, _SUM, _MAX, _MIN, _MEDIAN, _ROWS = range(7)
@@ -41,6 +47,214 @@ def onset_strength(*, y=None, sr=22050, S=None, lag=1, max_size=1, ref=None, det
     odf_all = onset_strength_multi(y=y, sr=sr, S=S, lag=lag, max_size=max_size, ref=ref, detrend=detrend, center=center, feature=feature, aggregate=aggregate, channels=None,
                                    **kwargs)
     return odf_all[..., 0, :]
+
+
+# ---- onset_detect / onset_backtrack ---------------------------------------------------------------------------------------------------
+_PICK_KEYS = ("pre_max", "post_max", "pre_avg", "post_avg", "wait", "delta", "method")
+
+
+def onset_detect(*, y=None, sr=22050, onset_envelope=None, hop_length=512, backtrack=False, energy=None, units="frames", normalize=True, sparse=True, **kwargs):
+    """Onset events by peak picking on the onset strength envelope; drop-in for ``librosa.onset.onset_detect`` (``librosa/onset.py:31-214``).
+
+    ``sparse=True`` (one-dimensional input only): ``int64`` frame indices, or samples / seconds with ``units``; ``sparse=False``: a bool array
+    of the envelope's shape.  ``kwargs`` go to ``util.peak_pick``; the defaults are the reference's (30 ms / 0 ms maximum windows, 100 ms /
+    100 ms mean windows, 30 ms dead time, ``delta=0.07``, in frames of ``sr / hop_length``).  ``normalize=True`` shifts and scales every row to
+    [0, 1] in the envelope's precision, bit for bit as NumPy does; ``backtrack=True`` reads the normalised envelope (or ``energy``).  A
+    normalised envelope without a non-zero entry, or with a non-finite one anywhere, gives no onsets: an empty array or an all-False one.
+
+    Every argument is checked before any device work: ``y`` / ``onset_envelope``, ``units``, ``backtrack`` with ``sparse=False``, the rank
+    with ``sparse=True``, ``hop_length``, the names in ``kwargs`` and the picker's ranges.  The reference checks ``units`` last, ``backtrack``
+    and the picker's ranges only when the envelope has something to pick, and the rank inside the picker; so the two differ only where a call
+    is wrong in one of these AND the envelope is empty of onsets: the reference returns the empty result, this raises.  An integer envelope
+    with ``normalize=True`` raises ``TypeError`` as the reference's in-place division does; with ``normalize=False`` it is picked in float64,
+    and a float16 envelope in float64 too.  The caller's arrays are never modified."""
+    if onset_envelope is None and y is None:
+        raise ParameterError("y or onset_envelope must be provided")
+    src = onset_envelope if onset_envelope is not None else y
+    if not is_torch_tensor(src):
+        src = np.asarray(src)
+    if sparse and units not in ("frames", "samples", "time"):
+        raise ParameterError(f"Invalid unit type: {units}")
+    if backtrack and not sparse:
+        raise ParameterError("onset backtracking is only supported if sparse=True")
+    if sparse and src.ndim != 1:  # from y the envelope's rank is y's rank
+        raise ParameterError(f"sparse=True (default) does not support {src.ndim}-dimensional inputs. Either set sparse=False or process each dimension independently.")
+    if src.ndim == 0:
+        raise ParameterError("onset_detect needs an input of at least one dimension")
+    if hop_length is None or not util.is_positive_int(hop_length):
+        raise ParameterError(f"hop_length={hop_length} must be a positive integer")
+    unknown = [k for k in kwargs if k not in _PICK_KEYS]
+    if unknown:
+        raise TypeError(f"peak_pick() got an unexpected keyword argument '{unknown[0]}'")
+    kw = dict(kwargs)
+    kw.setdefault("pre_max", 0.03 * sr // hop_length)  # 30ms (onset.py:184-189)
+    kw.setdefault("post_max", 0.00 * sr // hop_length + 1)  # 0ms
+    kw.setdefault("pre_avg", 0.10 * sr // hop_length)  # 100ms
+    kw.setdefault("post_avg", 0.10 * sr // hop_length + 1)  # 100ms
+    kw.setdefault("wait", 0.03 * sr // hop_length)  # 30ms
+    kw.setdefault("delta", 0.07)
+    params = _peaks.prepare(**kw)
+    if backtrack and energy is not None:
+        if not is_torch_tensor(energy):
+            energy = np.asarray(energy)
+        if energy.ndim != 1:
+            raise ParameterError(f"energy must be one-dimensional, given energy.shape={tuple(energy.shape)}")
+    job = dict(params=params, normalize=bool(normalize), backtrack=bool(backtrack), energy=energy if backtrack else None)
+
+    if onset_envelope is not None:
+        real = _peaks.row_dtype(src)
+        if real is None and normalize:
+            raise TypeError(f"Cannot cast ufunc 'divide' output from dtype('float64') to dtype('{_arrays.numpy_dtype_of(src)}') with casting rule 'same_kind'")
+        got = _detect_given(src, real or np.dtype(np.float64), job)
+    else:
+        got = _detect_fused(src, sr, hop_length, job)
+    lead = tuple(src.shape[:-1])
+    n = int(src.shape[-1]) if onset_envelope is not None else 1 + int(src.shape[-1]) // int(hop_length)
+    on_device = is_torch_tensor(src)
+    if got is None:  # no onsets to grab (onset.py:176-180)
+        if on_device:
+            torch = _arrays._torch()
+            onsets = torch.zeros(0, dtype=torch.int64, device=src.device) if sparse else torch.zeros(lead + (n,), dtype=torch.bool, device=src.device)
+        else:
+            onsets = np.array([], dtype=int) if sparse else np.zeros(lead + (n,), dtype=bool)
+    else:
+        rows, prev = got
+        onsets = _peaks.to_bool(rows).reshape(lead + (n,))
+        if sparse:
+            onsets = _peaks.to_indices(onsets)
+            if backtrack:
+                onsets = _gather_minima(onsets, prev.reshape(-1))
+    if not sparse:
+        return onsets
+    if on_device:
+        if units == "samples":
+            onsets = onsets * int(hop_length)
+        elif units == "time":
+            samples = (onsets * int(hop_length)).to(_arrays._torch().float64)
+            onsets = samples / _arrays._torch().full_like(samples, float(sr))  # (a tensor divisor: a correctly rounded division, NumPy's bits; a scalar one is a multiplication by 1 / sr)
+        return onsets
+    if units == "samples":
+        onsets = _convert.frames_to_samples(onsets, hop_length=hop_length)
+    elif units == "time":
+        onsets = _convert.frames_to_time(onsets, hop_length=hop_length, sr=sr)
+    return onsets
+
+
+def _gather_minima(events, prev):
+    """``minima[match_events(events, minima, right=False)]`` from the row of preceding minima: events past the end take the last minimum;
+    an empty event list and a negative event raise as ``util.match_events`` does (``util/matching.py:279-305``)."""
+    if int(events.shape[0]) == 0:
+        raise ParameterError("Attempting to match empty event list")
+    if int(events.min()) < 0:
+        raise ParameterError("Cannot match events with right=False and min(events_to) > min(events_from)")
+    m = int(prev.shape[0])
+    if is_torch_tensor(prev):
+        torch = _arrays._torch()
+        return prev[torch.clamp(events, max=m - 1)].to(torch.int64)
+    return prev[np.minimum(events, m - 1)].astype(np.int64)
+
+
+def _prev_minimum(sess, e_ptr, m, real):
+    p_ptr, handle = sess.output((1, m), np.int32)
+    sess.ctx.prev_minimum_exec(e_ptr, 1, m, real, p_ptr)
+    return sess.result(handle)
+
+
+def _detect_rows(sess, env_ptr, batch, n, real, job):
+    """The picker (and the preceding minima) on a device envelope -> (handle of the uint8 rows, previous-minimum row or None, something to grab)."""
+    own = job["backtrack"] and job["energy"] is None
+    handle, norm_ptr, nonzero, finite = _peaks.pick_rows(sess, env_ptr, batch, n, real, job["params"], normalize=job["normalize"], keep_norm=own, status=True)
+    prev = None
+    if job["backtrack"] and nonzero and finite:
+        if own:
+            prev = _prev_minimum(sess, norm_ptr, n, real)
+        else:
+            energy = job["energy"]
+            e_real = _peaks.row_dtype(energy) or np.dtype(np.float64)
+            e = energy if is_torch_tensor(energy) and sess.is_torch else _spectrum._as_like(sess, energy.detach().cpu().numpy() if is_torch_tensor(energy) else energy)
+            m = int(energy.shape[0])
+            if m == 0:
+                raise ParameterError("energy must not be empty")
+            prev = _prev_minimum(sess, sess.input_raw(e, e_real), m, e_real)
+    return handle, prev, bool(nonzero and finite)
+
+
+def _detect_given(env, real, job):
+    on_device = is_torch_tensor(env)
+    lead, n = tuple(env.shape[:-1]), int(env.shape[-1])
+    batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if n == 0 or batch == 0:
+        return None
+    if not on_device:
+        # onset.py:164-176 on the host: an envelope with nothing to grab needs no device (the device repeats the arithmetic bit for bit)
+        e = env.astype(real, copy=False)
+        if job["normalize"]:
+            e = e - np.min(e, keepdims=True, axis=-1)
+            e /= np.max(e, keepdims=True, axis=-1) + util.tiny(e)
+        if not e.any() or not np.all(np.isfinite(e)):
+            return None
+    sess = _arrays.Session(env if on_device else np.empty(0))
+    try:
+        env_ptr = sess.input_raw(env.reshape(batch, n), real)
+        handle, prev, alive = _detect_rows(sess, env_ptr, batch, n, real, job)
+        rows = sess.result(handle)
+    finally:
+        sess.close()
+    return (rows, prev) if alive else None
+
+
+def _detect_fused(y, sr, hop_length, job):
+    side = {}
+
+    def stage(sess, env_ptr, rows, n_env, real):
+        handle, side["prev"], side["alive"] = _detect_rows(sess, env_ptr, rows, n_env, real, job)
+        return handle, 1, n_env
+
+    rows = _strength_then(y, sr=sr, hop_length=hop_length, stage=stage)  # (..., 1, n)
+    return (rows, side["prev"]) if side["alive"] else None
+
+
+def onset_backtrack(events, energy):
+    """Each event moved back to the nearest preceding local minimum of ``energy``; drop-in for ``librosa.onset.onset_backtrack``
+    (``librosa/onset.py:370-441``).
+
+    A minimum is frame 0, or a frame ``1 <= j <= len(energy) - 2`` with ``energy[j] <= energy[j - 1]`` and ``energy[j] < energy[j + 1]``.  The
+    result has ``events.shape`` (``int64``; two events may share a minimum).  As in the reference: an event past the end takes the last
+    minimum, ``len(energy) < 3`` sends every event to 0, and an empty event list or a negative event raises ``ParameterError``.  The minima
+    are found on the device; a device tensor among the arguments gives a device tensor."""
+    on_device = is_torch_tensor(events) or is_torch_tensor(energy)
+    if not is_torch_tensor(events):
+        events = np.asarray(events)
+    if not is_torch_tensor(energy):
+        energy = np.asarray(energy)
+    if energy.ndim != 1:
+        raise ParameterError(f"energy must be one-dimensional, given energy.shape={tuple(energy.shape)}")
+    shape = tuple(events.shape)
+    flat = events.reshape(-1)
+    if int(flat.shape[0]) == 0:
+        raise ParameterError("Attempting to match empty event list")
+    if _arrays.numpy_dtype_of(flat).kind == "f":
+        flat = flat.floor().to(_arrays._torch().int64) if is_torch_tensor(flat) else np.floor(flat).astype(np.int64)
+    if int(flat.min()) < 0:
+        raise ParameterError("Cannot match events with right=False and min(events_to) > min(events_from)")
+    m = int(energy.shape[0])
+    like = energy if is_torch_tensor(energy) else events
+    if m < 3:  # no interior frame: the only minimum is the padded 0
+        if on_device:
+            torch = _arrays._torch()
+            return torch.zeros(shape, dtype=torch.int64, device=like.device)
+        return np.zeros(shape, dtype=np.int64)
+    real = _peaks.row_dtype(energy) or np.dtype(np.float64)
+    sess = _arrays.Session(like if on_device else np.empty(0))
+    try:
+        if sess.is_torch and not is_torch_tensor(energy):
+            energy = _spectrum._as_like(sess, energy)
+        prev = _prev_minimum(sess, sess.input_raw(energy, real), m, real).reshape(-1)
+    finally:
+        sess.close()
+    if is_torch_tensor(prev) and not is_torch_tensor(flat):
+        flat = _arrays._torch().from_numpy(np.ascontiguousarray(flat, dtype=np.int64)).to(prev.device)
+    return _gather_minima(flat, prev).reshape(shape)
 
 
 def onset_strength_multi(*, y=None, sr=22050, S=None, n_fft=2048, hop_length=512, lag=1, max_size=1, ref=None, detrend=False, center=True, feature=None, aggregate=None,
