@@ -361,6 +361,21 @@ int lra_peak_pick_exec(lra_ctx* ctx, const void* x, int64_t batch, int64_t n, in
  * e[j] <= e[j - 1] and e[j] < e[j + 1]: onset_backtrack(events, energy) is out[min(events, m - 1)]. */
 int lra_prev_minimum_exec(lra_ctx* ctx, const void* energy, int64_t batch, int64_t m, int dtype, void* out);
 
+/* ---- chroma: librosa.feature.chroma_stft / chroma_cqt (feature/spectral.py:1285-1293, 1407-1421) ------------------------------------
+ * raw[c][t] = sum_f W[c][f] X[f][t]; has_threshold != 0: raw < threshold -> 0 (chroma_cqt); then util.normalize(raw, norm, axis=-2) with
+ * fill=None (util/utils.py:959-1011): the frame's length from float64 magnitudes, 1 where it is below `tiny` of `dtype`, one division. */
+#define LRA_CHROMA_NORM_NONE 0
+#define LRA_CHROMA_NORM_L1 1
+#define LRA_CHROMA_NORM_L2 2
+#define LRA_CHROMA_NORM_INF 3
+/* X: `dtype` (device), element (b, f, t) at b * batch_stride + f * bin_stride + t * frame_stride (elements).  bin_stride == 1 (the layout
+ * lra_spectrogram_exec writes, rows possibly padded) and frame_stride == 1 (a C-contiguous [b][f][t] array) are the two fast forms; any
+ * other strides are served by the second.  W: [n_chroma][n_bins] `dtype` (device).  out: [batch][n_chroma][n_frames] `dtype`.  work: at
+ * least 256 bytes of device scratch.  nonfinite (host, may be NULL): 1 when some raw value, after the threshold, is NaN or infinite (the
+ * reference then raises "Input must be finite", for every norm) -- reading it waits for the stream. */
+int lra_chroma_exec(lra_ctx* ctx, const void* X, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
+                    const void* W, int64_t n_chroma, int norm, double threshold, int has_threshold, void* out, void* work, int* nonfinite);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

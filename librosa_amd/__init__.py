@@ -9,7 +9,7 @@ path and its inverse, behind librosa's own Python signatures.
 Only this path and the callers right next to it are provided -- ``magphase``, decibel scaling, ``feature.mfcc``, ``griffinlim``,
 ``phase_vocoder`` / ``effects.time_stretch``, ``decompose.hpss`` / ``effects.hpss``, ``pcen``, ``cqt`` / ``vqt``, ``stream``, ``resample``, ``onset.onset_strength`` / ``onset_strength_multi``,
 ``onset.onset_detect`` / ``onset_backtrack``, ``util.peak_pick``,
-``feature.tempogram`` / ``fourier_tempogram`` / ``tempo``, ``beat.beat_track`` and the frame / sample / time converters (see
+``feature.tempogram`` / ``fourier_tempogram`` / ``tempo``, ``beat.beat_track``, ``feature.chroma_stft`` / ``chroma_cqt`` (``tuning`` as a number) and the frame / sample / time converters (see
 DESIGN.md for the scope table).  Host-side Python validates
 arguments exactly like the reference and builds the small float64 tables (window, mel basis, window
 sum-square); all signal arithmetic runs in hand-written HIP kernels through the C ABI declared in

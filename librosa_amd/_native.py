@@ -113,6 +113,8 @@ SIGNATURES = {
     "lra_cqt_octave_supported": (c_int, [c_int]),
     "lra_cqt_octave_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int]),
     "lra_magnitude_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "lra_chroma_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
+                        POINTER(c_int)]),
     "lra_magphase_exec": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_double, c_int]),
     "lra_hpss_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_int]),
     "lra_dct_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_void_p, c_void_p, c_int, c_double]),
@@ -617,6 +619,17 @@ class Context:
         _check(self.lib.lra_cqt_recursion_exec(self.handle, c_void_p(y_ptr), batch, ctypes.cast(octaves, c_void_p), len(octaves), PAD_MODES[pad_mode], c_void_p(sqrt_len_ptr) if sqrt_len_ptr else None,
                                                c_void_p(out_ptr), n_frames, int(n_total), c_void_p(taps_ptr) if taps_ptr else None, int(n_taps), int(first), c_void_p(scratch_ptr) if scratch_ptr else None,
                                                int(scratch_bytes), int(bool(overlap)), dtype_code(dtype)))
+
+    CHROMA_NORMS = {None: 0, 1: 1, 2: 2, float("inf"): 3}   # the LRA_CHROMA_NORM_* values
+
+    def chroma_exec(self, x_ptr, batch, n_bins, n_frames, batch_stride, bin_stride, frame_stride, dtype, w_ptr, n_chroma, norm_code, threshold, out_ptr, work_ptr):
+        """Chroma projection + threshold + per-frame normalisation (``include/librosa_amd.h``: lra_chroma_exec); ``threshold=None`` skips the
+        threshold.  Returns True when some raw value is not finite (this waits for the stream)."""
+        flag = c_int(0)
+        _check(self.lib.lra_chroma_exec(self.handle, c_void_p(x_ptr), int(batch), int(n_bins), int(n_frames), int(batch_stride), int(bin_stride), int(frame_stride), dtype_code(dtype),
+                                        c_void_p(w_ptr), int(n_chroma), int(norm_code), 0.0 if threshold is None else float(threshold), int(threshold is not None), c_void_p(out_ptr),
+                                        c_void_p(work_ptr), byref(flag)))
+        return bool(flag.value)
 
     def magnitude_exec(self, d_ptr, mag_ptr, count, dtype):
         _check(self.lib.lra_magnitude_exec(self.handle, c_void_p(d_ptr), c_void_p(mag_ptr), count, dtype_code(dtype)))

@@ -140,13 +140,16 @@ def _plan(sr, hop_length, fmin, n_bins, intervals, gamma, bins_per_octave, filte
 
 
 def vqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, intervals="equal", gamma=None, bins_per_octave=12, tuning=0.0, filter_scale=1, norm=1, sparsity=0.01,
-        window="hann", scale=True, pad_mode="constant", res_type="soxr_hq", dtype=None, check_finite=True):
+        window="hann", scale=True, pad_mode="constant", res_type="soxr_hq", dtype=None, check_finite=True, _post=None):
     """Variable-Q transform; drop-in for ``librosa.vqt`` (``librosa/core/constantq.py:820-1122``).
 
     Returns ``(..., n_bins, n_frames)`` complex (complex64 for float32 audio).  ``y`` may be a device tensor (a device tensor is
     returned; ``check_finite=False`` -- an extension, as for ``stft`` -- then skips ``valid_audio``'s finite test, whose device flag costs one
     host synchronisation per call: back-to-back calls otherwise cannot overlap their launches with the previous call's kernels).  Not provided: ``tuning=None`` (needs the pitch tracker behind ``estimate_tuning``), named just-intonation interval
     sets (``intervals`` must be ``"equal"`` or an explicit list).  See the module docstring for ``res_type``.
+
+    ``_post(sess, ptr, batch, n_frames, n_bins, real) -> (handle, rows)`` (internal) chains further device work on the [batch][n_frames][n_bins]
+    complex result before anything is downloaded (``feature.chroma_cqt``); the result is then the real ``(..., rows, n_frames)`` array of ``handle``.
     """
     if not isinstance(intervals, str):
         intervals = tuple(float(v) for v in intervals)
@@ -275,6 +278,10 @@ def vqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, intervals="equal",
         if OVERLAP_OCTAVES and not native:
             ctx.side(ctx.SIDE_JOIN)
         overlapped = False
+        if _post is not None:
+            if not sess.is_torch:
+                sess._keep.append(handle[0])  # the transform itself is not downloaded
+            handle, post_rows = _post(sess, out_ptr, batch, n_frames, n_bins, real)
         if check and ctx.nonfinite_read() and not _all_finite(y):
             raise ParameterError("Audio buffer is not finite everywhere")
         res = sess.result(handle)
@@ -282,11 +289,13 @@ def vqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, intervals="equal",
         if overlapped:   # an error between fork and join: nothing of this call may still run when its buffers are released
             ctx.side(ctx.SIDE_END)
         sess.close()
+    if _post is not None:
+        return res.reshape(lead + (int(post_rows), n_frames))
     return _arrays.swap_last_two(res.reshape(lead + (n_frames, n_bins)))
 
 
 def cqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, tuning=0.0, filter_scale=1, norm=1, sparsity=0.01, window="hann", scale=True,
-        pad_mode="constant", res_type="soxr_hq", dtype=None, check_finite=True):
+        pad_mode="constant", res_type="soxr_hq", dtype=None, check_finite=True, _post=None):
     """Constant-Q transform; drop-in for ``librosa.cqt`` (``librosa/core/constantq.py:42-225``): the ``gamma=0`` case of :func:`vqt`.
     Not provided: ``tuning=None`` -- the reference estimates the tuning with its pitch tracker
     (``core/constantq.py:318-319, 985-986`` -> ``estimate_tuning``), which is outside this library's scope: pass a number (default 0.0).
@@ -294,4 +303,4 @@ def cqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12
     ``"fft"`` / ``"scipy"`` are pinned against the reference.
     """
     return vqt(y, sr=sr, hop_length=hop_length, fmin=fmin, n_bins=n_bins, intervals="equal", gamma=0, bins_per_octave=bins_per_octave, tuning=tuning, filter_scale=filter_scale,
-               norm=norm, sparsity=sparsity, window=window, scale=scale, pad_mode=pad_mode, res_type=res_type, dtype=dtype, check_finite=check_finite)
+               norm=norm, sparsity=sparsity, window=window, scale=scale, pad_mode=pad_mode, res_type=res_type, dtype=dtype, check_finite=check_finite, _post=_post)

@@ -403,7 +403,11 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
 
     ``post(sess, mel_ptr, batch, n_mels, n_frames, real) -> (handle, rows)`` (mel only) chains further device work on the mel
     spectrogram before anything is downloaded (``feature.mfcc``); the result then has ``rows`` rows instead of ``n_mels``.  ``post`` may
-    return ``(handle, rows, cols)`` when its result has ``cols`` columns instead of ``n_frames`` (``onset.onset_strength_multi``)."""
+    return ``(handle, rows, cols)`` when its result has ``cols`` columns instead of ``n_frames`` (``onset.onset_strength_multi``).
+
+    With ``kind="power"`` the hook is ``post(sess, s_ptr, batch, n_bins, n_frames, pitch, real) -> (handle, rows)``: ``s_ptr`` is the power
+    spectrogram [batch][n_frames][pitch] on the device (``pitch >= n_bins`` elements between the rows of consecutive frames); the spectrogram is
+    not downloaded and the result is the ``(..., rows, n_frames)`` array of ``handle`` (``feature.chroma_stft``)."""
     need_device_check = _validate_audio(y, check_finite)
     y, hop, fft_window, center, pad_mode = _prepare_stft(y, n_fft, hop_length, win_length, window, center, pad_mode)
     in_dtype = _arrays.numpy_dtype_of(y)
@@ -521,6 +525,10 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
                 ctx.spectrogram_exec(plan, y_ptr, batch, n, y_stride, power, ptr)
             else:
                 ctx.stft_exec_strided(plan, 1, y_ptr, batch, n, y_stride, power, ptr, pitch)
+            if post is not None:
+                if not sess.is_torch:
+                    sess._keep.append(handle[0])  # the spectrogram itself is not downloaded
+                handle, post_rows = post(sess, ptr, batch, n_bins, n_frames, pitch, real)
         else:
             n_mels = int(mel_basis.shape[0])
             mel_plan = ctx.mel_plan(np.ascontiguousarray(mel_basis, dtype=real))
@@ -540,6 +548,8 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
         sess.close()
     if kind == "mel":
         return res.reshape(lead + (n_mels, n_frames))
+    if kind == "power" and post is not None:
+        return res.reshape(lead + (int(post_rows), n_frames))
     if pitch != n_bins:
         res = res.view(lead + (n_frames, pitch))[..., :n_bins]  # the padding stays behind the view
     res = _arrays.swap_last_two(res.reshape(lead + (n_frames, n_bins)))  # (..., n_bins, n_frames) view

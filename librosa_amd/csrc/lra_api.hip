@@ -49,6 +49,7 @@
 #include "lra_rhythm_launch.h"
 #include "lra_beat_launch.h"
 #include "lra_peaks_launch.h"
+#include "lra_chroma_launch.h"
 
 using namespace lra;
 
@@ -3218,6 +3219,42 @@ int lra_prev_minimum_exec(lra_ctx* ctx, const void* energy, int64_t batch, int64
     if (m > 0x7fffffffLL - 64) return fail(LRA_EINVAL, "prev_minimum: too many frames per row");
     peaks::MinArgs a{energy, m, (int*)out};
     LRA_HIP(peaks::launch_prev_minimum(a, batch, dtype == LRA_F64, ctx->stream));
+    return LRA_OK;
+}
+
+int lra_chroma_exec(lra_ctx* ctx, const void* X, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
+                    const void* W, int64_t n_chroma, int norm, double threshold, int has_threshold, void* out, void* work, int* nonfinite) {
+    LRA_BIND(ctx);
+    if (nonfinite) *nonfinite = 0;
+    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "chroma: dtype must be LRA_F32 or LRA_F64");
+    if (norm != LRA_CHROMA_NORM_NONE && norm != LRA_CHROMA_NORM_L1 && norm != LRA_CHROMA_NORM_L2 && norm != LRA_CHROMA_NORM_INF) return fail(LRA_EINVAL, "chroma: unknown norm");
+    if (batch < 0 || n_bins < 0 || n_frames < 0 || n_chroma < 0) return fail(LRA_EINVAL, "chroma: negative size");
+    if (batch == 0 || n_frames == 0 || n_chroma == 0) return LRA_OK;
+    if (n_bins > 0x7fffffffLL || n_chroma > 0x7fffffffLL) return fail(LRA_EINVAL, "chroma: too many bins or rows");
+    if ((n_bins > 0 && (!X || !W)) || !out || !work) return fail(LRA_EINVAL, "null data pointer");
+    if (batch_stride < 0 || bin_stride < 0 || frame_stride < 0) return fail(LRA_EINVAL, "chroma: negative stride");
+    chroma::Args a{};
+    a.x = X;
+    a.batch_stride = batch_stride;
+    a.bin_stride = bin_stride;
+    a.frame_stride = frame_stride;
+    a.n_bins = (int)n_bins;
+    a.n_frames = n_frames;
+    a.w = W;
+    a.n_chroma = (int)n_chroma;
+    a.norm = norm;
+    a.has_thr = has_threshold != 0;
+    a.thr = threshold;
+    a.out = out;
+    a.flag = (int*)work;
+    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
+    LRA_HIP(chroma::launch_chroma(a, batch, dtype == LRA_F64, ctx->stream));
+    if (nonfinite) {
+        int h = 0;
+        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        LRA_HIP(hipStreamSynchronize(ctx->stream));
+        *nonfinite = h != 0;
+    }
     return LRA_OK;
 }
 

@@ -2,8 +2,8 @@
 
 These tables are tiny (a window of n_fft samples, a 128 x 1025 filterbank with 2018 non-zeros) and
 are built once per configuration on the host with the same float64 arithmetic as the reference, so
-they are bit-identical to ``librosa.filters.get_window`` (:914-977), ``mel`` (:116-251) and
-``window_sumsquare`` (:1268-1339); the device receives them as plan constants.
+they are bit-identical to ``librosa.filters.get_window`` (:914-977), ``mel`` (:116-251), ``chroma`` (:255-394),
+``cq_to_chroma`` (:737-861) and ``window_sumsquare`` (:1268-1339); the device receives them as plan constants.
 """
 from __future__ import annotations
 
@@ -17,7 +17,7 @@ from .core.convert import fft_frequencies, mel_frequencies
 from .util import utils as _u
 from .util.exceptions import ParameterError
 
-__all__ = ["get_window", "mel", "window_sumsquare", "window_bandwidth", "wavelet", "wavelet_lengths"]
+__all__ = ["get_window", "mel", "chroma", "cq_to_chroma", "window_sumsquare", "window_bandwidth", "wavelet", "wavelet_lengths"]
 
 
 def get_window(window, Nx, *, fftbins=True):
@@ -105,6 +105,90 @@ def mel_cached(*, sr, n_fft, n_mels=128, fmin=0.0, fmax=None, htk=False, norm="s
     for m in msgs:
         warnings.warn(m, stacklevel=3)
     return B
+
+
+# ---------------------------------------------------------------------------------------------------
+# chroma filter banks: librosa/filters.py:255-394 (FFT bins -> pitch classes) and :737-861 (constant-Q bins -> pitch classes)
+# Unlike the mel bank these are dense -- every weight of ``chroma`` is a Gaussian tail, non-zero in float32 -- so the device applies
+# them as plain dot products (csrc/lra_chroma.h).
+# ---------------------------------------------------------------------------------------------------
+_C1_HZ = 440.0 * (2.0 ** ((24 - 69) / 12))  # note_to_hz("C1"): MIDI note 24
+
+
+def chroma(*, sr, n_fft, n_chroma=12, tuning=0.0, ctroct=5.0, octwidth=2, norm=2, base_c=True, dtype=np.float32):
+    """Chroma filter bank, shape ``(n_chroma, 1 + n_fft // 2)``: a Gaussian bump per pitch class around every FFT bin's (fractional) chroma
+    position, as wide as the bin is in chroma units, each bin's column scaled to unit ``norm``, times a Gaussian octave weighting centred
+    ``ctroct`` octaves above A0 with half-width ``octwidth`` (``None``: flat).  ``base_c``: row 0 is C, else A."""
+    n_chroma_f = float(n_chroma)
+    a440 = 440.0 * 2.0 ** (tuning / n_chroma)
+    hz = np.linspace(0, sr, n_fft, endpoint=False)[1:]            # every bin of the full transform but DC
+    position = n_chroma * np.log2(hz / (float(a440) / 16))        # chroma units above A0's octave start (hz_to_octs)
+    # the DC bin gets a made-up place 1.5 octaves below bin 1
+    position = np.concatenate(([position[0] - 1.5 * n_chroma], position))
+    width = np.concatenate((np.maximum(position[1:] - position[:-1], 1.0), [1]))
+    dist = np.subtract.outer(position, np.arange(0, n_chroma, dtype="d")).T
+    half = np.round(n_chroma_f / 2)
+    dist = np.remainder(dist + half + 10 * n_chroma, n_chroma) - half   # wrapped into [-n_chroma / 2, n_chroma / 2)
+    weights = np.exp(-0.5 * (2 * dist / np.tile(width, (n_chroma, 1))) ** 2)
+    weights = _u.normalize(weights, norm=norm, axis=0)
+    if octwidth is not None:
+        weights *= np.exp(-0.5 * (((position / n_chroma - ctroct) / octwidth) ** 2))[np.newaxis, :]
+    if base_c:
+        weights = np.roll(weights, -3 * (n_chroma // 12), axis=0)
+    return np.ascontiguousarray(weights[:, : int(1 + n_fft / 2)], dtype=dtype)
+
+
+def cq_to_chroma(n_input, *, bins_per_octave=12, n_chroma=12, fmin=None, window=None, base_c=True, dtype=np.float32):
+    """Map of ``n_input`` constant-Q bins (``bins_per_octave`` per octave, the first at ``fmin``, default C1) onto ``n_chroma`` pitch classes,
+    shape ``(n_chroma, n_input)``: each class sums the ``bins_per_octave / n_chroma`` bins centred on it in every octave; ``window``: a
+    vector the rows are convolved with."""
+    merge = float(bins_per_octave) / n_chroma
+    midi_first = 12 * (np.log2(np.asanyarray(_C1_HZ if fmin is None else fmin)) - np.log2(440.0)) + 69   # hz_to_midi
+    if np.mod(merge, 1) != 0:
+        raise ParameterError("Incompatible CQ merge: input bins must be an integer multiple of output bins.")
+    octave = np.roll(np.repeat(np.eye(n_chroma), int(merge), axis=1), -int(merge // 2), axis=1)
+    n_octaves = np.ceil(float(n_input) / bins_per_octave)
+    bank = np.tile(octave, int(n_octaves))[:, :n_input]
+    pitch = np.mod(midi_first, 12)   # of the first bin, in semitones above C
+    if not base_c:
+        pitch = pitch - 9
+    bank = np.roll(bank, int(np.round(pitch * (n_chroma / 12.0))), axis=0).astype(dtype)
+    if window is not None:
+        bank = scipy.signal.convolve(bank, np.atleast_2d(window), mode="same")
+    return bank
+
+
+def _frozen(x):
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=64)
+def _chroma_cached(sr, n_fft, n_chroma, tuning, ctroct, octwidth, norm, base_c, dtype_str):
+    return _frozen(chroma(sr=sr, n_fft=n_fft, n_chroma=n_chroma, tuning=tuning, ctroct=ctroct, octwidth=octwidth, norm=norm, base_c=base_c, dtype=np.dtype(dtype_str)))
+
+
+def chroma_cached(*, sr, n_fft, n_chroma=12, tuning=0.0, ctroct=5.0, octwidth=2, norm=2, base_c=True, dtype=np.float32):
+    """``chroma`` memoised on its (hashable) arguments; the array is read-only."""
+    try:
+        return _chroma_cached(sr, n_fft, n_chroma, tuning, ctroct, octwidth, norm, bool(base_c), np.dtype(dtype).str)
+    except TypeError:  # unhashable argument
+        return chroma(sr=sr, n_fft=n_fft, n_chroma=n_chroma, tuning=tuning, ctroct=ctroct, octwidth=octwidth, norm=norm, base_c=base_c, dtype=dtype)
+
+
+@functools.lru_cache(maxsize=64)
+def _cq_to_chroma_cached(n_input, bins_per_octave, n_chroma, fmin, base_c, dtype_str):
+    return _frozen(cq_to_chroma(n_input, bins_per_octave=bins_per_octave, n_chroma=n_chroma, fmin=fmin, base_c=base_c, dtype=np.dtype(dtype_str)))
+
+
+def cq_to_chroma_cached(n_input, *, bins_per_octave=12, n_chroma=12, fmin=None, window=None, base_c=True, dtype=np.float32):
+    """``cq_to_chroma`` memoised on its arguments where there is no ``window`` (an array); the array is then read-only."""
+    if window is None:
+        try:
+            return _cq_to_chroma_cached(n_input, bins_per_octave, n_chroma, fmin, bool(base_c), np.dtype(dtype).str)
+        except TypeError:
+            pass
+    return cq_to_chroma(n_input, bins_per_octave=bins_per_octave, n_chroma=n_chroma, fmin=fmin, window=window, base_c=base_c, dtype=dtype)
 
 
 # ---------------------------------------------------------------------------------------------------
