@@ -26,15 +26,6 @@
 #include <vector>
 
 #include "../../include/librosa_amd.h"
-#ifndef LRA_ISTFT16_DEFAULT
-#define LRA_ISTFT16_DEFAULT 0
-#endif
-#ifndef LRA_V3_DEFAULT
-#define LRA_V3_DEFAULT 1  // measured on two boxes, same buffer, alternating (profiles/r06_raw/c_*, d_*): complex STFT -1.3 % ... -2.0 %, |X|^2 +1 % (hence complex only)
-#endif
-#ifndef LRA_MEL_PC_DEFAULT
-#define LRA_MEL_PC_DEFAULT 1  // the producer / consumer fused mel kernel (lra_kernels_pc.h), ctx option "mel_pc": -0.8 ... -1.9 % against the one-wave kernel on four boxes (profiles/r06_raw), never slower
-#endif
 #define LRA_FUSED_EXTERN  // the fused kernels are instantiated in lra_inst.hip (parallel build), see lra_fused.h
 #include "lra_fused.h"
 #include "lra_mel.h"
@@ -95,7 +86,7 @@ struct lra_ctx {
     int opt_generic_mel = 0;         // force the generic banded mel path (tests)
     int opt_lds_pad = 0;             // extra dynamic LDS per workgroup (occupancy experiments)
     int opt_v2 = 1;                  // second-generation forward kernel where it applies (lra_kernels2.h)
-    int opt_istft16 = LRA_ISTFT16_DEFAULT;  // inverse, n_fft = 2048 f32, hop = n_fft / {2, 4, 8, 16}: radices 4, 16, 16 with 16-byte spectrum loads (variant 7) instead of 8, 8, 16
+    int opt_istft16 = 0;             // inverse, n_fft = 2048 f32, hop = n_fft / {2, 4, 8, 16}: radices 4, 16, 16 with 16-byte spectrum loads (variant 7) instead of 8, 8, 16
     int opt_placement_retry = 0;     // lra_malloc_placed: candidate allocations to time before keeping the best (0 = its `tries` argument decides)
     struct PlacedAlloc {             // one lra_malloc_placed result: a reserved virtual range backed by physical handles created and mapped in order
         size_t padded = 0;
@@ -112,8 +103,10 @@ struct lra_ctx {
     size_t placed_va_spent = 0;
     static constexpr size_t kPlacedVaBudget = (size_t)4 << 40;  // 4 TiB of address space per context, then lra_malloc_placed declines (callers fall back to an ordinary allocation)
     double placed_best_gbps = 0.0;   // best write-stream rate any candidate of this context has shown (the early-exit yardstick)
-    int opt_v3 = LRA_V3_DEFAULT;     // n_fft = 2048 f32: the radix 16-16-4 form with 16-byte row pieces (variant 6, lra_kernels2.h third form); 1: complex epilogue, 2: |X|^p too
-    int opt_mel_pc = LRA_MEL_PC_DEFAULT;  // fused mel, n_fft = 2048 f32: the producer / consumer kernel (lra_kernels_pc.h) instead of stft2_kernel<OUT_MELR>
+    int opt_v3 = 1;                  // n_fft = 2048 f32: the radix 16-16-4 form with 16-byte row pieces (variant 6, lra_kernels2.h third form); 1: complex epilogue, 2: |X|^p too
+                                     // (measured on two boxes, same buffer, alternating (profiles/r06_raw/c_*, d_*): complex STFT -1.3 % ... -2.0 %, |X|^2 +1 %, hence complex only)
+    int opt_mel_pc = 1;              // fused mel, n_fft = 2048 f32: the producer / consumer kernel (lra_kernels_pc.h) instead of stft2_kernel<OUT_MELR>
+                                     // (-0.8 ... -1.9 % against the one-wave kernel on four boxes (profiles/r06_raw), never slower)
     int opt_mel_many = 1;            // mel plans of n_fft = 512 with more than 64 bands are built for the eight-bands-per-thread kernel shape (read at lra_mel_plan_create)
     int opt_cqt_merge = 1;           // lra_cqt_recursion_exec: 1 = octaves 1-2 in one launch beside the later halvings, 3 .. in one launch behind the chain (round 6); 2 = octaves 1 .. in one launch per frame length behind the chain (round 5); 0 = one launch per octave on the side stream
     int opt_hpss_tile = 1;           // hpss: a thread per 4 x 4 tile with shared sorted cores (hpss_tile_kernel); 0: a thread per element (A/B)
@@ -392,10 +385,7 @@ template <class T> struct StftLaunch {
         if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, 0>;
         if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, 0>;
         if constexpr (sizeof(T) == 4) {  // row-aligned hops (n_fft/4, n_fft/8, ...): the fast ring addressing, f32 only
-#ifndef LRA_MEL_RA
-#define LRA_MEL_RA 1
-#endif
-            if (ring_rows_aligned<Cfg>(a.hop) && (LRA_MEL_RA || MODE == OUT_COMPLEX || MODE == OUT_POWER)) {
+            if (ring_rows_aligned<Cfg>(a.hop)) {
                 kern = stft_kernel<Cfg, MODE, POW_TWO, 1>;
                 if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, 1>;
                 if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, 1>;
@@ -1326,9 +1316,8 @@ int istft_run(lra_istft_plan* p, const void* D, int64_t batch, int64_t d_batch_s
             const int halo = (N + p->hop - 1) / p->hop - 1;
             // halo frames are recomputed by the neighbouring group: worth it while they are a third of the work at most; everything else takes the inverse transform alone
             // (mixed_irfft_kernel) + the gather kernel below, which beats both the recomputing kernel at larger LDS tiers and the rocFFT path (round 6: 480 / 120 2.84 ->
-            // 1.62 ms, 800 / 200 2.77 -> 1.63, 1200 / 300 4.8 -> 2.25, 3200 / 800 4.75 -> 2.52; LRA_MIXED_INV_RULE_X2 moves the border for A/B)
-            static const int rule_x2 = std::getenv("LRA_MIXED_INV_RULE_X2") ? std::atoi(std::getenv("LRA_MIXED_INV_RULE_X2")) : 4;
-            if (fmax - halo >= 1 && 2 * (fmax - halo) >= rule_x2 * halo) {
+            // 1.62 ms, 800 / 200 2.77 -> 1.63, 1200 / 300 4.8 -> 2.25, 3200 / 800 4.75 -> 2.52)
+            if (fmax - halo >= 1 && fmax - halo >= 2 * halo) {
                 const void* nrm = wss;
                 if (!wss_is_norm) {
                     LRA_TRY(p->norm.ensure((size_t)out_len * sizeof(T)));
@@ -1886,10 +1875,9 @@ int lra_ctx_side(lra_ctx* ctx, int mode) {
         if (ctx->on_side) return fail(LRA_EINVAL, "lra_ctx_side: already on the side stream");
         if (!ctx->side_stream) {
             // the side stream carries work that runs BESIDE a dependent chain on the caller's stream (octave transforms beside the halvings): lowest
-            // priority, so that the chain's short kernels are dispatched ahead of it (LRA_SIDE_PRIO=0: default priority, development A/B)
+            // priority, so that the chain's short kernels are dispatched ahead of it
             int least = 0, greatest = 0;
-            const char* knob = std::getenv("LRA_SIDE_PRIO");
-            if ((!knob || std::atoi(knob) != 0) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+            if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
                 LRA_HIP(hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, least));
             else
                 LRA_HIP(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
@@ -2167,16 +2155,14 @@ int lra_malloc_placed(lra_ctx* ctx, size_t bytes, int row_bytes, int64_t rows_pe
     // its slowest (0.735 against 0.672-0.694 for hipMalloc, profiles/r06_raw/u_*): the write stream decides, per buffer.
     for (int i = 0; i < tries; ++i) {
         Cand c{nullptr, {}, 0.f};
-        static const size_t chunk_mb = []() { const char* e = std::getenv("LRA_PLACED_CHUNK_MB"); const long v = e ? std::atol(e) : 0; return (size_t)(v >= 2 && v <= 4096 ? v : 64); }();  // (development knob)
-        static const int kinds = []() { const char* e = std::getenv("LRA_PLACED_KINDS"); return e ? std::atoi(e) : 3; }();  // (development knob: 1 = hipMalloc only, 2 = assembled only, 3 = both)
-        const bool plain = kinds == 1 || (kinds == 3 && (i % 2) == 0);
+        const bool plain = (i % 2) == 0;
         if (plain) {
             c.pa.plain = true;
             c.pa.padded = bytes;
             hipError_t e = hipMalloc(&c.p, bytes);
             rc = e == hipSuccess ? LRA_OK : fail(e == hipErrorOutOfMemory ? LRA_ENOMEM : LRA_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
         } else {
-            rc = placed_create(ctx, bytes, chunk_mb << 20, &c.p, &c.pa);
+            rc = placed_create(ctx, bytes, (size_t)64 << 20, &c.p, &c.pa);
         }
         if (rc != LRA_OK) {
             if (!cands.empty()) { rc = LRA_OK; (void)hipGetLastError(); }  // (out of memory for one more candidate: keep the best so far)
@@ -3593,8 +3579,7 @@ int lra_cqt_recursion_exec(lra_ctx* ctx, const void* y, int64_t batch, const lra
         }
         // Round 6: with five or more octaves, octaves 1 and 2 go out in a launch of their own on the side stream as soon as their signals exist, beside the
         // remaining (short) halvings, which cannot fill the chip; the rest follows the chain as before (cqt_merge = 2: everything behind the chain).
-        static const int early_knob = std::getenv("LRA_CQT_EARLY") ? std::atoi(std::getenv("LRA_CQT_EARLY")) : 3;  // (development: one past the last early octave)
-        int early_end = (ctx->opt_cqt_merge == 1 && n_octaves >= 5) ? std::min(std::max(early_knob, 2), n_octaves - 1) : 1;
+        int early_end = (ctx->opt_cqt_merge == 1 && n_octaves >= 5) ? std::min(3, n_octaves - 1) : 1;  // one past the last early octave
         for (int i = 2; i < early_end; ++i)
             if (octaves[i].n_fft != octaves[1].n_fft) early_end = 1;  // (one launch serves one frame length)
         for (int i = 0; i + 1 < n_octaves && rc == LRA_OK; ++i) {

@@ -29,13 +29,8 @@
 
 // branch-probability hints: hipcc's block placement then keeps the rare paths (np.pad folds at a clip's edges, the non-finite flag,
 // piece lists beyond the hoisted prefix) out of the frame loop's fall-through chain
-#ifndef LRA_NO_EXPECT
 #define LRA_LIKELY(x) __builtin_expect(!!(x), 1)
 #define LRA_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#else
-#define LRA_LIKELY(x) (x)
-#define LRA_UNLIKELY(x) (x)
-#endif
 
 namespace lra {
 
@@ -68,7 +63,7 @@ template <class T> LRA_HD cx<T> cmul_mi(cx<T> a) { return mk<T>(a.y, -a.x); }
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
 #error "librosa_amd kernels assume 64-wide wavefronts"
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(LRA_NO_PK_ASM)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define LRA_PK_ASM 1
 namespace pk {
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -221,45 +216,26 @@ template <class T> LRA_HD cx<T> pmul(cx<T> a, cx<T> b) { return mk<T>(a.x * b.x,
 #define LRA_ARM_END(tag) ((void)0)
 #endif
 
-// Wave priority at the phase boundaries of the frame loops (s_setprio; P < 0: no instruction; nothing in the host simulator).  With two
+// Wave priority at the phase boundaries of the frame loops (s_setprio; nothing in the host simulator).  With two
 // waves per SIMD the issue arbiter otherwise serves the older wave first whatever it is doing; a wave in its transform passes (dense
 // vector work) ahead of one in its epilogue (short dependent LDS round trips) is worth 5-6 % of the fused mel kernel
 // (profiles/r04_experiments.md 10).
 template <int P> LRA_HD void lra_setprio() {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (P >= 0) __builtin_amdgcn_s_setprio(P);
+    __builtin_amdgcn_s_setprio(P);
 #endif
 }
-#ifndef LRA_V1_PRIO_A   // first-generation forward kernel, mel epilogue (stft_block): transform 3 / split + accumulate 0 / band combine 1 (n_fft 512, 80 mels, 256 x 30 s:
-                        // hop 128 0.994 -> 0.946 ms, hop 160 0.849 -> 0.821 ms; profiles/r04_experiments.md 10)
-#define LRA_V1_PRIO_A 3
-#endif
-#ifndef LRA_V1_PRIO_B
-#define LRA_V1_PRIO_B 0
-#endif
-#ifndef LRA_V1_PRIO_B3
-#define LRA_V1_PRIO_B3 1
-#endif
-#ifndef LRA_V1_PRIO_CA  // first-generation kernels, complex / power epilogues (experiment hooks; -1 = no instruction)
-#define LRA_V1_PRIO_CA -1
-#endif
-#ifndef LRA_V1_PRIO_CS
-#define LRA_V1_PRIO_CS -1
-#endif
-#ifndef LRA_I_PRIO_A
-#define LRA_I_PRIO_A -1
-#endif
-#ifndef LRA_I_PRIO_B
-#define LRA_I_PRIO_B -1
-#endif
+// first-generation forward kernel, mel epilogue (stft_block): transform 3 / split + accumulate 0 / band combine 1 (n_fft 512, 80 mels, 256 x 30 s:
+// hop 128 0.994 -> 0.946 ms, hop 160 0.849 -> 0.821 ms; profiles/r04_experiments.md 10).  The first generation's complex / power epilogues
+// and the inverse kernel set no priority.
+constexpr int kV1PrioA = 3, kV1PrioB = 0, kV1PrioB3 = 1;
 
 // Per-lane select under a mask that is held in an SGPR pair: c ? a : b as v_cndmask_b32_e64 (VOP3).  hipcc emits the VOP2 form with
 // the implicit VCC operand for most selects, and on gfx950 a v_cndmask_b32_e32 issued directly behind another one stalls the
 // SIMD's vector pipe for ~16 cycles (scripts/valu_probe2.hip: 9.7 ns per instruction back to back at one or two waves per SIMD
 // against 2.0 ns for the VOP3 form and 1.1 ns when another VALU instruction sits in between) -- the lane-0 selects of the
 // mirrored split come in pairs (real / imaginary half), i.e. every second one paid that.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(LRA_NO_SEL_ASM)
-#define LRA_SEL_ASM 1
+#if defined(__HIP_DEVICE_COMPILE__)
 using LaneMask = unsigned long long;
 __device__ __forceinline__ LaneMask lane_mask(bool c) { return __builtin_amdgcn_ballot_w64(c); }
 __device__ __forceinline__ float sel_mask(LaneMask m, bool, float a, float b) {
@@ -280,10 +256,8 @@ template <class T> LRA_HD cx<T> sel_mask(LaneMask m, bool c, cx<T> a, cx<T> b) {
 // Round 4 reads the piece totals as whole (A, B) pairs (ds_read_b64: 64 banks; a 4-byte read of one half of an 8-byte slot can only ever
 // land on 16 of its 32 banks, a built-in 2-way conflict), for which the plain pitch TF models best (scripts/lds_model.py: 57 LDS cycles per
 // frame for the 16 reads against 90 with 4-byte reads at pitch TF + 1).
-#ifndef LRA_MEL_RS_PITCH_EXTRA
-#define LRA_MEL_RS_PITCH_EXTRA 0
-#endif
-LRA_HD int mel_runs_pitch(int tf_count, int layout) { return layout == 1 ? tf_count + LRA_MEL_RS_PITCH_EXTRA : tf_count; }
+constexpr int kMelRsPitchExtra = 0;
+LRA_HD int mel_runs_pitch(int tf_count, int layout) { return layout == 1 ? tf_count + kMelRsPitchExtra : tf_count; }
 
 // pad modes for centred framing (np.pad modes the reference forwards, core/spectrum.py:287)
 enum PadMode : int { PAD_CONSTANT = 0, PAD_REFLECT = 1, PAD_EDGE = 2, PAD_SYMMETRIC = 3 };
@@ -376,7 +350,6 @@ template <class V> inline void lds_st_addr(Lds l, int addr, V v) { lds_st<V>(l, 
 #define LRA_RAW_TID(tid) (tid)
 template <class T> inline T fast_div(T x, T w) { return x / w; }
 template <class V> inline void stream_store(V* p, V v) { *p = v; }
-template <class V> inline void stream_store16(V* p, V v) { *p = v; }
 template <class V> inline V stream_load(const V* p) { return *p; }
 template <class T> inline void store4_unaligned(T* p, T a, T b, T c, T d) { p[0] = a; p[1] = b; p[2] = c; p[3] = d; }
 #define LRA_PHASE(NT, tid) for (int tid = 0; tid < (NT); ++tid) { ::lra::sim::state().cur_tid = tid;
@@ -396,21 +369,16 @@ template <class T> inline void store4_unaligned(T* p, T a, T b, T c, T d) { p[0]
 struct Lds {
     char* base;
 };
-// LRA_LDS_NOMERGE (experiment): 8-byte LDS reads are issued as volatile loads, which keeps hipcc from fusing neighbouring pairs
-// into ds_read2_b64 / ds_read2st64_b64.  /opt/skills/guides/MI355X_MICROARCH.md (LDS table) prices ds_read2_b64 at 8 LDS cycles per
-// wave-instruction against 2 for ds_read_b64, i.e. the fused form at HALF the rate of the two reads it replaces.
-#ifndef LRA_LDS_NOMERGE
-#define LRA_LDS_NOMERGE 1
-#endif
+// 8-byte LDS reads are issued as volatile loads, which keeps hipcc from fusing neighbouring pairs into ds_read2_b64 / ds_read2st64_b64:
+// ds_read2_b64 costs 8 LDS cycles per wave-instruction against 2 for ds_read_b64, i.e. the fused form runs at HALF the rate of the two
+// reads it replaces.
 template <class V> LRA_HD V lds_ld(Lds l, int byte_off) {
-#if LRA_LDS_NOMERGE
     if constexpr (sizeof(V) == 8) {
         typedef float f2v __attribute__((ext_vector_type(2)));
         // (explicit LDS address space: address-space inference leaves volatile accesses alone, and a flat volatile load is no DS op)
         const f2v t = *(const volatile __attribute__((address_space(3))) f2v*)(l.base + byte_off);
         return __builtin_bit_cast(V, t);
     }
-#endif
     return *reinterpret_cast<const V*>(l.base + byte_off);
 }
 template <class V> LRA_HD void lds_st(Lds l, int byte_off, V v) { *reinterpret_cast<V*>(l.base + byte_off) = v; }
@@ -434,25 +402,9 @@ template <class V> __device__ __forceinline__ void lds_st_addr(Lds, int addr, V 
 // x / w for normal w: v_rcp_f32 + v_mul (<= 1 ulp) instead of the ~12-instruction IEEE division sequence
 __device__ __forceinline__ float fast_div(float x, float w) { return x * __builtin_amdgcn_rcpf(w); }
 __device__ __forceinline__ double fast_div(double x, double w) { return x / w; }
-// Output that is written once and not read again by this kernel: a non-temporal (streaming) store.
-#ifndef LRA_NT_STORE
-#define LRA_NT_STORE 0  // measured on MI355X: no gain for the spectrum rows (the L2 write-back path already streams them)
-#endif
-template <class V> __device__ __forceinline__ void stream_store(V* p, V v) {
-#if LRA_NT_STORE
-    if constexpr (sizeof(V) == 8) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(__builtin_bit_cast(f2v, v), reinterpret_cast<f2v*>(p));
-    } else if constexpr (sizeof(V) == 16) {
-        typedef double d2v __attribute__((ext_vector_type(2)));
-        __builtin_nontemporal_store(__builtin_bit_cast(d2v, v), reinterpret_cast<d2v*>(p));
-    } else {
-        __builtin_nontemporal_store(v, p);
-    }
-#else
-    *p = v;
-#endif
-}
+// Output that is written once and not read again by this kernel.  A plain store: the non-temporal form measured no gain for the
+// spectrum rows on MI355X (the L2 write-back path already streams them).
+template <class V> __device__ __forceinline__ void stream_store(V* p, V v) { *p = v; }
 // four consecutive words as ONE store where the element type allows it (global_store_dwordx4; the pointer need only be element-aligned:
 // the hardware takes unaligned vector stores, and the type says so to the compiler)
 template <class T> __device__ __forceinline__ void store4_unaligned(T* p, T a, T b, T c, T d) {
@@ -465,33 +417,8 @@ template <class T> __device__ __forceinline__ void store4_unaligned(T* p, T a, T
         p[0] = a; p[1] = b; p[2] = c; p[3] = d;
     }
 }
-// Input that is read once: optionally a non-temporal load (experiment, LRA_NT_LOAD)
-#ifndef LRA_NT_LOAD
-#define LRA_NT_LOAD 0
-#endif
-template <class V> __device__ __forceinline__ V stream_load(const V* p) {
-#if LRA_NT_LOAD
-    if constexpr (sizeof(V) == 8) {
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        return __builtin_bit_cast(V, __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p)));
-    }
-#endif
-    return *p;
-}
-// 16-byte piece of a row that is written once, whole 16-byte pieces only, neighbours back to back: non-temporal
-// (measured on the store stream of the STFT: +8 % alone, +16 % with the XCD-aware workgroup map)
-#ifndef LRA_V2_NT
-#define LRA_V2_NT 1
-#endif
-template <class V> __device__ __forceinline__ void stream_store16(V* p, V v) {
-    static_assert(sizeof(V) == 16, "16-byte pieces");
-    typedef float f4v __attribute__((ext_vector_type(4)));
-#if LRA_V2_NT
-    __builtin_nontemporal_store(__builtin_bit_cast(f4v, v), reinterpret_cast<f4v*>(p));
-#else
-    *reinterpret_cast<f4v*>(p) = __builtin_bit_cast(f4v, v);
-#endif
-}
+// Input that is read once (a plain load)
+template <class V> __device__ __forceinline__ V stream_load(const V* p) { return *p; }
 // Phase boundary.  WAVE = true: every lane that exchanges data through LDS across this boundary is
 // in the same wave64 (a wave's DS instructions execute in order), so a compiler-level fence is
 // enough and the waves of the workgroup are free to drift apart; otherwise a workgroup barrier.
@@ -506,11 +433,7 @@ template <bool WAVE> __device__ __forceinline__ void phase_sync() {
         // (s_waitcnt lgkmcnt(0); s_barrier -- no vmcnt drain, checked in the ISA); it is spelled out so that the
         // in-flight prefetch loads and output stores can never be made to wait here by a stronger fence.  The
         // "memory" clobber keeps the compiler from moving LDS accesses across the barrier.
-#ifdef LRA_FULL_BARRIER  // experiments only
-        __syncthreads();
-#else
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
     }
 }
 // The thread index is re-read through an opaque move at the top of every phase.  Without it hipcc hoists
@@ -518,9 +441,7 @@ template <bool WAVE> __device__ __forceinline__ void phase_sync() {
 // live for the whole kernel) and then spills the values that matter, e.g. the prefetch registers.
 __device__ __forceinline__ int phase_tid() {
     int t = (int)threadIdx.x;
-#ifndef LRA_NO_TID_LAUNDER
     asm volatile("" : "+v"(t));
-#endif
     return t;
 }
 #define LRA_PHASE(NT, tid) { const int tid = ::lra::phase_tid();

@@ -110,10 +110,7 @@ template <class T, class F> inline bool dispatch_logm(int logm, int variant, F&&
 // larger workgroup.  When a frame fits one wave: 256 threads = 4 slots (two such workgroups share a CU and
 // drift apart; measured +2 % over one 512-thread workgroup whose 8 waves start every phase together)
 template <class Cfg> struct MelCfgOf {
-#ifndef LRA_MELNT
-#define LRA_MELNT 256
-#endif
-    static constexpr int MELNT = Cfg::TF <= 64 ? LRA_MELNT : (2 * Cfg::TF <= 1024 ? 2 * Cfg::TF : Cfg::TF);
+    static constexpr int MELNT = Cfg::TF <= 64 ? 256 : (2 * Cfg::TF <= 1024 ? 2 * Cfg::TF : Cfg::TF);
     using type = typename Cfg::template with_nt<MELNT>;
 };
 // ... and the shape for MANY bands per frame thread (round 5): 128 threads = eight slots of 16 threads.  The thread count doubles as the tag by which

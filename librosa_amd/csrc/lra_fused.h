@@ -36,11 +36,9 @@ __global__ __launch_bounds__(Cfg::NT, Cfg::MIN_WAVES) void stft_kernel(lra::Stft
 // Second-generation forward kernel (lra_kernels2.h): PCM ring in registers, mirrored last pass with the split step in
 // registers.  HD = n_fft / hop.  The register budget is sized for 3 waves per SIMD (12 slots of 8.7 KB per CU) where the
 // kernel fits it without spilling (n_fft = 2048 with hop <= n_fft/4, i.e. at most 4 sample pairs in flight per thread).
-#ifndef LRA_V3_WAVES
-#define LRA_V3_WAVES 3  // waves per SIMD the radix 16-16-4 form is compiled for
-#endif
+constexpr int kV3Waves = 3;  // waves per SIMD the radix 16-16-4 form is compiled for
 template <class Cfg, int HD, int MODE, int PM>
-__global__ __launch_bounds__(Cfg::NT, (Cfg::NT > 256 ? 1 : (Cfg::TF == 64 && HD >= 4 && PM != lra::POW_GENERAL && MODE != lra::OUT_MELR ? (Cfg::PLAN == 1 ? LRA_V3_WAVES : 3) : 2))) void stft2_kernel(lra::StftArgs<typename Cfg::real> a, const typename Cfg::real* __restrict__ y,
+__global__ __launch_bounds__(Cfg::NT, (Cfg::NT > 256 ? 1 : (Cfg::TF == 64 && HD >= 4 && PM != lra::POW_GENERAL && MODE != lra::OUT_MELR ? (Cfg::PLAN == 1 ? kV3Waves : 3) : 2))) void stft2_kernel(lra::StftArgs<typename Cfg::real> a, const typename Cfg::real* __restrict__ y,
                                                                                   void* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) char lra_smem[];
     lra::Lds lds;

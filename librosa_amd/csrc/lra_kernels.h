@@ -21,10 +21,6 @@
 // simulator used by tests (see lra_common.h).
 #pragma once
 
-#ifndef LRA_ABLATE
-#define LRA_ABLATE 0  // kernel experiments (scripts/gpu_probe.py builds), 0 in the product
-#endif
-
 #include <cmath>
 #include <limits>
 
@@ -134,17 +130,13 @@ template <class Cfg> LRA_HD int lane_of(int tid) { return (int)((unsigned)tid % 
 // n_fft 1024, 16 at 512) and their threads take 4 / 8 bands each -- round 5: with two, 96 of 128 bands of an n_fft = 512 frame went through the
 // table path (two dependent LDS reads per piece, one 4-byte store per band and frame): 1.84 ms against 0.31 ms for the transform itself.  Their
 // pair segments are a few bins wide, so two hoisted pieces per list cover them (longer lists take the rest from the table).
-#ifndef LRA_MELR_NB_SMALL
-#define LRA_MELR_NB_SMALL 4  // bands per thread where TF <= 16 (8 was measured: the n_fft = 512 kernel then needs 276 VGPRs, and 20 spilled registers cost more than the table path)
-#endif
-#ifndef LRA_MELR_PH_SMALL
-#define LRA_MELR_PH_SMALL 3  // hoisted pieces per list there (same box, n_fft 512 / hop 128 / 80 bands: 2 -> 0.85, 3 -> 0.75, 4 -> 0.77 ms; two bands x four pieces before: 0.95)
-#endif
+constexpr int kMelrNbSmall = 4;  // bands per thread where TF <= 16 (8 was measured: the n_fft = 512 kernel then needs 276 VGPRs, and 20 spilled registers cost more than the table path)
+constexpr int kMelrPhSmall = 3;  // hoisted pieces per list there (same box, n_fft 512 / hop 128 / 80 bands: 2 -> 0.85, 3 -> 0.75, 4 -> 0.77 ms; two bands x four pieces before: 0.95)
 // (TF = 32, n_fft = 1024: four bands per thread with two hoisted pieces measured 0.79 against 0.83 ms at 128 bands but 0.78 against 0.68 ms at 80, whose
 // wider segments need the longer hoisted lists: it keeps two bands per thread)
 // `many`: the 128-thread workgroup shape of lra_dispatch.h (MelManyCfgOf): eight bands, one hoisted piece per list
-constexpr int melr_nb_of_tf(int tf, bool many = false) { return tf >= 32 ? 2 : (many ? 8 : LRA_MELR_NB_SMALL); }
-constexpr int melr_ph_of_tf(int tf, bool many = false) { return tf >= 32 ? 4 : (many ? 1 : LRA_MELR_PH_SMALL); }  // (also the minimum list length the host builds: lra_api.hip)
+constexpr int melr_nb_of_tf(int tf, bool many = false) { return tf >= 32 ? 2 : (many ? 8 : kMelrNbSmall); }
+constexpr int melr_ph_of_tf(int tf, bool many = false) { return tf >= 32 ? 4 : (many ? 1 : kMelrPhSmall); }  // (also the minimum list length the host builds: lra_api.hip)
 template <class Cfg> constexpr bool melr_many() { return Cfg::TF == 16 && Cfg::NT == 128; }
 template <class Cfg> constexpr int melr_nb() { return melr_nb_of_tf(Cfg::TF, melr_many<Cfg>()); }
 template <class Cfg> constexpr int melr_ph() { return melr_ph_of_tf(Cfg::TF, melr_many<Cfg>()); }
@@ -406,9 +398,7 @@ template <class Cfg, bool RA> LRA_HD void stft_ring_load_pass0(const StftArgs<ty
             }
         }
     }
-#if LRA_ABLATE != 2
     pass_dft<Cfg, 0>(rg, tf, a.tw);
-#endif
     pass_write<Cfg, 0>(v, fr, tf);
 }
 
@@ -647,19 +637,11 @@ template <class Cfg, int MODE, int PM> LRA_HD void stft_split_store(const StftAr
             km = M;
             if (valid && a.nonfinite_flag && !(std::fabs(xk.x) <= std::numeric_limits<T>::max())) LRA_ATOMIC_OR(a.nonfinite_flag, 1u);
         } else {
-#if LRA_ABLATE == 2  // experiment: stores only
-            xk = rg.v[2 * i]; xm = rg.v[2 * i + 1];
-#else
             split_pair<T>(rg.v[2 * i], rg.v[2 * i + 1], Cfg::HOIST ? rg.twr[i] : a.twr[k], xk, xm);
-#endif
             km = M - k;
         }
         if (MODE == OUT_COMPLEX) {
-#if LRA_ABLATE == 1 || LRA_ABLATE == 4  // experiment: compute everything, store (practically) nothing
-            if (valid && xk.x == (T)12345.678) { Dk[i * Cfg::TF] = xk; Dm[-i * Cfg::TF] = xm; }
-#else
             if (valid) { stream_store(&Dk[i * Cfg::TF], xk); stream_store(&Dm[-i * Cfg::TF], xm); }
-#endif
         } else {
             const T pk = spec_power<T, PM>(xk, a.power), pm = spec_power<T, PM>(xm, a.power);
             if (MODE == OUT_POWER) {
@@ -668,12 +650,8 @@ template <class Cfg, int MODE, int PM> LRA_HD void stft_split_store(const StftAr
                 const C wk = lds_ld<C>(sh, k * (int)sizeof(C)), wm = lds_ld<C>(sh, km * (int)sizeof(C));
                 // AB[k] sits at the padded slot k + k/R: a thread's run of R consecutive bins then starts
                 // R+1 slots after its neighbour's, which makes the run reads of mel2_gather conflict-free
-#if LRA_ABLATE == 13  // experiment: no mel epilogue at all (keep the power computation alive)
-                if (wk.x * pk + wm.x * pm == (T)12345.678) a.Mel[k] = pk;
-#else
                 lds_st<C>(fr, ab_slot<Cfg>(k) * (int)sizeof(C), mk<T>(wk.x * pk, wk.y * pk));
                 lds_st<C>(fr, ab_slot<Cfg>(km) * (int)sizeof(C), mk<T>(wm.x * pm, wm.y * pm));
-#endif
             } else {
                 lds_st<T>(fr, k * (int)sizeof(T), pk);
                 lds_st<T>(fr, km * (int)sizeof(T), pm);
@@ -708,9 +686,6 @@ template <class Cfg, int MODE, int PM> LRA_HD void stft_split_store(const StftAr
 // j with 15 - j by itself, butterfly 0 pairs j with 16 - j, which thread 0 absorbs by acting as b = s with its registers shifted
 // by one (eight lane-0 selects; its slot 7 is X[M/2], its v[0] gives X[0] and X[M]).
 // Per frame and thread: 16 LDS writes + 16 reads and two workgroup barriers less than the split through LDS, for 16 swaps.
-#ifndef LRA_MIRROR_TWR_BASE
-#define LRA_MIRROR_TWR_BASE 1
-#endif
 template <class Cfg> constexpr bool mirror32_cfg_ok() {
     constexpr int pl = Cfg::P - 1;
     return Cfg::P >= 2 && Cfg::R == 16 && Cfg::HOIST && sizeof(typename Cfg::real) == 4 && Cfg::logr(pl) == 4 && Cfg::TF % 64 == 0 && Cfg::TF == (Cfg::M >> 4) &&
@@ -724,21 +699,18 @@ template <class Cfg> LRA_HD int mirror32_bfly(int tf) {
 template <class Cfg> LRA_HD int mirror32_kbase(int tf) { return tf == 0 ? Cfg::TF : mirror32_bfly<Cfg>(tf); }
 template <class Cfg> LRA_HD bool mirror32_swaps(int tf) { return tf != 0 && tf != 32; }
 
-// prologue: the last pass's twiddles of butterfly mirror32_bfly(tf) and the split twiddles of the thread's pair slots replace
+// prologue: the last pass's twiddles of butterfly mirror32_bfly(tf) and the split twiddle of the thread's first pair slot replace
 // what hoist_tables loaded for butterfly tf
 template <class Cfg> LRA_HD void mirror32_hoist(FftRegs<Cfg>& rg, int tf, const typename Cfg::cplx* __restrict__ tw, const typename Cfg::cplx* __restrict__ twr) {
     if constexpr (mirror32_cfg_ok<Cfg>()) {
         load_pass_twiddles<Cfg, Cfg::P - 1>(rg.treg, mirror32_bfly<Cfg>(tf), tw);
-        const int kb = mirror32_kbase<Cfg>(tf);
-        LRA_UNROLL
-        for (int q = 0; q < (LRA_MIRROR_TWR_BASE ? 1 : Cfg::R / 2); ++q) rg.twr[q] = twr[kb + q * Cfg::TF];
+        rg.twr[0] = twr[mirror32_kbase<Cfg>(tf)];
     }
 }
 // split twiddle of pair slot q: W_N^(kb + q s) = W_N^kb W_32^q (s = N / 32).  Only W_N^kb is kept in registers -- with all eight the
 // kernel needs 182 VGPRs, two workgroups per CU instead of three; seven complex products per frame are the cheaper side.
 template <class Cfg> LRA_HD typename Cfg::cplx mirror32_twr(const FftRegs<Cfg>& rg, int q) {
     using T = typename Cfg::real;
-    if (!LRA_MIRROR_TWR_BASE) return rg.twr[q];
     constexpr double c32[8] = {1.0, 0.98078528040323044913, 0.92387953251128675613, 0.83146961230254523708, 0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173, 0.19509032201612826785};
     if (q == 0) return rg.twr[0];
     const cx<T> c = mk<T>((T)c32[q], (T)-c32[8 - q]);  // exp(-2 pi i q / 32): cos = c32[q], sin = c32[8 - q]
@@ -816,9 +788,6 @@ template <class Cfg> LRA_HD void mel_flush_slot(const StftArgs<typename Cfg::rea
 // flush of the staging tile that iteration `it` of a slot (first frame f_slot) belongs to: the frames
 // staged so far in that tile, clipped to the clip's frame count
 template <class Cfg> LRA_HD void mel_flush_tile(const StftArgs<typename Cfg::real>& a, int clip, int f_slot, int it, int tile, int tf, Lds stage) {
-#if LRA_ABLATE == 14
-    if (a.n_mels != 12345) return;
-#endif
     const int f0 = f_slot + (it / tile) * tile;  // first frame of the staged tile
     int nv = a.n_frames - f0;
     const int staged = it % tile + 1;
@@ -879,9 +848,6 @@ template <class Cfg> LRA_HD void mel2_combine(const StftArgs<typename Cfg::real>
     using T = typename Cfg::real;
     using C = typename Cfg::cplx;
     constexpr int NB = Cfg::M + 1;
-#if LRA_ABLATE == 15
-    if (a.n_mels != 12345) return;
-#endif
     for (int m = tf; m < a.n_mels; m += Cfg::TF) {
         // both descriptors, then the first UNR pieces of both halves as ONE batch of (predicated) loads: a
         // single LDS round trip per mel band instead of one per chunk of each half; wider segments (rare:
@@ -1009,9 +975,6 @@ template <class Cfg, int PM> LRA_HD void melr_split_accumulate(const StftArgs<ty
     }
 }
 
-#ifndef LRA_MEL_PAIR_READS
-#define LRA_MEL_PAIR_READS 1
-#endif
 // prologue: per-thread constants of the run-ordered epilogue -> registers (restart factors; the first MELR_PHOIST
 // entries of both piece lists of mel bands tf and tf + TF)
 // `base`: byte offset added to every hoisted address (the second-generation kernel passes its slot's offset, so that the 16
@@ -1029,7 +992,7 @@ template <class Cfg, class RG> LRA_HD void melr_hoist(const StftArgs<typename Cf
             for (int q = 0; q < PH; ++q) {
                 const int ad = base + (m < a.n_mels ? a.melr_addr[(h * a.melr_pmax + q) * a.n_mels + m] : a.melr_zero);
                 // (the table addresses the B half of a pair for list 0; melr_combine reads whole pairs: keep the pair's address)
-                rg.mad[b][h * PH + q] = (LRA_MEL_PAIR_READS && sizeof(typename Cfg::real) == 4) ? (ad & ~(2 * (int)sizeof(typename Cfg::real) - 1)) : ad;
+                rg.mad[b][h * PH + q] = sizeof(typename Cfg::real) == 4 ? (ad & ~(2 * (int)sizeof(typename Cfg::real) - 1)) : ad;
             }
         }
     }
@@ -1039,15 +1002,8 @@ template <class Cfg, class RG> LRA_HD void melr_hoist(const StftArgs<typename Cf
 // The tile position is tied to the ABSOLUTE element index in the output (row starts are n_frames elements apart, not a multiple of
 // MT), so that every full burst is one aligned MT x sizeof(T) = 32-byte piece: unaligned 32-byte bursts each dirtied two HBM sectors
 // (306 MB written per launch for 169 MB of output).  A slot's first and last bursts are partial.
-#ifndef LRA_MEL_ALIGNED_BURSTS
-#define LRA_MEL_ALIGNED_BURSTS 1
-#endif
-#ifndef LRA_MEL_BURST16  // a whole tile as two 16-byte stores instead of eight predicated 4-byte ones
-#define LRA_MEL_BURST16 1
-#endif
 template <class Cfg, class RG> LRA_HD int melr_tile_slot(const StftArgs<typename Cfg::real>& a, int clip, int frame, int it, int b, long long row0) {
     constexpr int MT = RG::MELR_TILE;
-    if (!LRA_MEL_ALIGNED_BURSTS) return it & (MT - 1);
     // rows start 0 or 16 bytes into a 32-byte piece, alternating with the band's parity: with bands 2 tf and 2 tf + 1
     // per thread the phase is (clip, frame, b) only -- scalar, so the tile select and the flush branch stay scalar
     // (a per-lane phase made the flush run twice per MT frames under half masks: +2.8 % kernel time)
@@ -1055,9 +1011,10 @@ template <class Cfg, class RG> LRA_HD int melr_tile_slot(const StftArgs<typename
     return (int)((row0 + frame) & (MT - 1));
 }
 // stores slots max(0, s8 - it) .. s8 of a tile to row[0 ..) (row: the element of tile slot 0); a whole tile leaves as two 16-byte stores
+// instead of eight predicated 4-byte ones
 template <class T, int MT> LRA_HD void melr_burst_row(T* __restrict__ row, int s8, int it, const T (&mt)[MT]) {
     if constexpr (sizeof(T) == 4 && (MT == 8 || MT == 4)) {
-        if (LRA_MEL_BURST16 && s8 == MT - 1 && it >= MT - 1) {
+        if (s8 == MT - 1 && it >= MT - 1) {
             store4_unaligned(row, mt[0], mt[1], mt[2], mt[3]);
             if constexpr (MT == 8) store4_unaligned(row + 4, mt[4], mt[5], mt[6], mt[7]);
             return;
@@ -1094,7 +1051,7 @@ template <class Cfg, class RG> LRA_HD void melr_combine(const StftArgs<typename 
         for (int bb = b; bb < b + GB; ++bb) {
             LRA_UNROLL
             for (int q = 0; q < 2 * PH; ++q) {
-                if constexpr (LRA_MEL_PAIR_READS && sizeof(T) == 4) {
+                if constexpr (sizeof(T) == 4) {
                     const cx<T> pr = lds_ld<cx<T>>(rs_hoisted, rg.mad[bb][q]);  // (melr_hoist keeps the pair's address)
                     x[bb][q] = q < PH ? pr.y : pr.x;
                 } else {
@@ -1194,37 +1151,24 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
     // regions -- piece sums, staging tile -- are not touched by the FFT): combine(t) runs next to the ring
     // loads / pass 0 of frame t+1 and flush(t) next to its split reads, which saves two workgroup
     // barriers per frame and lets the loads of both overlap.  The last frame's pair runs after the loop.
-    constexpr bool DEFER = MODE == OUT_MEL2 && !(LRA_ABLATE >= 11 && LRA_ABLATE <= 13);
+    constexpr bool DEFER = MODE == OUT_MEL2;
     // The mel kernel has no spectrum stores to keep clear of (see the ring notes above), so it fetches the
     // next frame's samples late -- issued with the split reads, consumed after the piece sums -- which
     // keeps the NPF prefetch registers out of the FFT passes, where the register pressure peaks.
-#ifndef LRA_MEL_LATE_PF
-#define LRA_MEL_LATE_PF 1
-#endif
-    constexpr bool LATE_PF = DEFER && LRA_MEL_LATE_PF;
-    // Vector memory operations of a wave complete IN ORDER (one vmcnt for loads and stores): a wait for the prefetched
+    constexpr bool LATE_PF = DEFER;
+    // Every other epilogue fetches early.  Vector memory operations of a wave complete IN ORDER (one vmcnt for loads and stores): a wait for the prefetched
     // samples also waits for every store issued before those loads, and a spectrum store is acknowledged only ~1.5 us
     // after issue (a lone wave loses 1 400 of 5 200 cycles per frame to that wait).  So the loads of frame t+2 are issued
     // at the END of frame t, right after the ring took frame t+1's samples and BEFORE frame t's stores: the wait one
     // frame later is then s_waitcnt vmcnt(<stores of frame t+1>) and only covers stores that are two frames old.
-#ifndef LRA_PF_EARLY
-#define LRA_PF_EARLY 1
-#endif
-    constexpr bool PF_EARLY = !LATE_PF && LRA_PF_EARLY;
     // Complex / power epilogues: the split step works on registers and writes HBM only, so the frame needs ONE workgroup barrier
     // behind its split reads ("every wave has read the frame area"), and that one sits behind the stores: a wave that waits there
     // has its row already in flight.  (Frames of more than one wave only; 7 -> 6 barriers per frame at n_fft = 8192.)
-#ifndef LRA_SPLIT_ONE_BARRIER
-#define LRA_SPLIT_ONE_BARRIER 1
-#endif
-    constexpr bool SPLIT_NO_LDS = LRA_SPLIT_ONE_BARRIER && (MODE == OUT_COMPLEX || MODE == OUT_POWER);
+    constexpr bool SPLIT_NO_LDS = MODE == OUT_COMPLEX || MODE == OUT_POWER;
     // ... and where the last pass is one radix-16 butterfly per thread (n_fft = 8192), the split step's LDS round trip goes as well
-#ifndef LRA_MIRROR32
-#define LRA_MIRROR32 1
-#endif
     // (measured per ring form on the 256 x 30 s batch, n_fft = 8192, profiles/r03_experiments.md section 8: hop = n_fft / 16 -1 %, n_fft / 2 -9 %;
     // n_fft / 4 unchanged, n_fft / 8 and direct framing +3 ... +6 % -- those keep the split through LDS)
-    constexpr bool MIRROR = LRA_MIRROR32 && (RAM == 3 || RAM == 6 || LRA_MIRROR32 > 1) && mirror32_cfg_ok<Cfg>();
+    constexpr bool MIRROR = (RAM == 3 || RAM == 6) && mirror32_cfg_ok<Cfg>();
     constexpr int MID_END = Cfg::P - (MIRROR ? 1 : 0);  // passes 1 .. MID_END - 1 go through LRA_MID_PASS
     LRA_REGS(FftRegs<Cfg>, rg, Cfg::NT);
     LRA_PHASE(Cfg::NT, tid) {
@@ -1250,7 +1194,7 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
             stft_direct_fetch<Cfg>(a, clip, f_first + slot * iters, tf, LRA_R(rg));
         } else {
             stft_ring_fill<Cfg>(a, clip, f_first + slot * iters, tf, lds_sub(lds, slot * slot_bytes + stft_ring_off<Cfg>()));
-            if (PF_EARLY && iters > 1) stft_ring_prefetch<Cfg, RA>(a, clip, f_first + slot * iters + 1, tf, LRA_R(rg));
+            if (!LATE_PF && iters > 1) stft_ring_prefetch<Cfg, RA>(a, clip, f_first + slot * iters + 1, tf, LRA_R(rg));
         }
     } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
     int done = 0;  // frames of this workgroup's slots processed so far (uniform)
@@ -1259,14 +1203,10 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
         if (f_first + it >= a.n_frames) break;  // slot 0 has the smallest frame index: uniform exit
         LRA_TICK(0);
         if (!Cfg::HOIST) { LRA_LAUNDER(a.win); LRA_LAUNDER(a.tw); LRA_LAUNDER(a.twr); }
-        if (MODE == OUT_MELR) lra_setprio<LRA_V1_PRIO_A>();  // wave priority per phase, as in stft2_kernel (lra_kernels2.h): transform / split / epilogue / band combine
-        else if (MODE == OUT_COMPLEX || MODE == OUT_POWER) lra_setprio<LRA_V1_PRIO_CA>();  // (complex / power epilogues: transform, then un-split + stores)
+        if (MODE == OUT_MELR) lra_setprio<kV1PrioA>();  // wave priority per phase, as in stft2_kernel (lra_kernels2.h): transform / split / epilogue / band combine
         LRA_PHASE(Cfg::NT, tid) {
             const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
             const Lds sl = lds_sub(lds, slot * slot_bytes);
-#if LRA_ABLATE != 3 && LRA_ABLATE != 4  // experiments 3 / 4: no PCM loads in the frame loop (4: and no spectrum stores)
-            if (!DIRECT && !LATE_PF && !PF_EARLY && it + 1 < iters) stft_ring_prefetch<Cfg, RA>(a, clip, frame + 1, tf, LRA_R(rg));
-#endif
             if (DEFER && it > 0 && frame - 1 < a.n_frames)
                 mel2_combine<Cfg>(a, clip, frame - 1, tf, (it - 1) % tile, tile, lds_sub(lds, a.shared_off), lds_sub(sl, slot_bytes - mel2_psum_bytes<Cfg>(a.n_mels)), lds_sub(sl, stft_tile_off<Cfg>()));
             if (RHD > 1) regring_pass0<Cfg, RHD>(a, clip, frame, it == 0, it + 1 < iters, tf, LRA_R(rg), sl);
@@ -1274,11 +1214,9 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
             else stft_ring_load_pass0<Cfg, RA>(a, frame, tf, LRA_R(rg), lds_sub(sl, stft_ring_off<Cfg>()), sl);
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
         LRA_TICK(1);
-#if LRA_ABLATE != 2
         LRA_MID_PASS_TO(Cfg, MID_END, 1, rg, lds, a.tw, slot_bytes)
         LRA_MID_PASS_TO(Cfg, MID_END, 2, rg, lds, a.tw, slot_bytes)
         LRA_MID_PASS_TO(Cfg, MID_END, 3, rg, lds, a.tw, slot_bytes)
-#endif
         if constexpr (MIRROR) {
             // last pass (butterfly mirror32_bfly), exchange across the wave's halves, split + stores from the registers; the ONE
             // workgroup barrier ("every wave has read the frame area") sits behind the stores
@@ -1290,7 +1228,6 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
             LRA_PHASE(Cfg::NT, tid) {
                 LRA_HALF_SWAP8(rg, tid, Cfg::R / 2, mirror32_swaps<Cfg>(lane_of<Cfg>(tid)));
             } LRA_PHASE_END_SYNC(true)
-            if (MODE == OUT_COMPLEX || MODE == OUT_POWER) lra_setprio<LRA_V1_PRIO_CS>();
             LRA_PHASE(Cfg::NT, tid) {
                 const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
                 mirror32_split_store<Cfg, MODE, PM>(a, clip, frame, frame < a.n_frames, tf, LRA_R(rg));
@@ -1305,23 +1242,20 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
             if (LATE_PF && it + 1 < iters) stft_ring_prefetch<Cfg, RA>(a, clip, frame + 1, tf, LRA_R(rg));
             if constexpr (MODE == OUT_MELR) split_read_runs<Cfg>(LRA_R(rg), sl, tf);
             else split_read<Cfg>(LRA_R(rg), sl, tf);
-#if LRA_ABLATE != 3 && LRA_ABLATE != 4
             if (!DIRECT && !LATE_PF && it + 1 < iters) stft_ring_advance<Cfg, RA>(a, clip, frame + 1, tf, LRA_R(rg), lds_sub(sl, stft_ring_off<Cfg>()));
-            if (!DIRECT && PF_EARLY && it + 2 < iters) stft_ring_prefetch<Cfg, RA>(a, clip, frame + 2, tf, LRA_R(rg));
-#endif
+            if (!DIRECT && !LATE_PF && it + 2 < iters) stft_ring_prefetch<Cfg, RA>(a, clip, frame + 2, tf, LRA_R(rg));
             if (DEFER && tile > 1 && it > 0 && it % tile == 0)  // the tile that frame it-1 completed
                 mel_flush_tile<Cfg>(a, clip, f_first + slot * iters, it - 1, tile, tf, lds_sub(sl, stft_tile_off<Cfg>()));
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC || SPLIT_NO_LDS)
         LRA_TICK(8);
-        if (MODE == OUT_MELR) lra_setprio<LRA_V1_PRIO_B>();
-        else if (MODE == OUT_COMPLEX || MODE == OUT_POWER) lra_setprio<LRA_V1_PRIO_CS>();
+        if (MODE == OUT_MELR) lra_setprio<kV1PrioB>();
         LRA_PHASE(Cfg::NT, tid) {
             const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
             if constexpr (MODE == OUT_MELR) melr_split_accumulate<Cfg, PM>(a, frame < a.n_frames, tf, LRA_R(rg), lds_sub(lds, slot * slot_bytes), lds_sub(lds, a.shared_off));
             else stft_split_store<Cfg, MODE, PM>(a, clip, frame, frame < a.n_frames, tf, LRA_R(rg), lds_sub(lds, slot * slot_bytes), lds_sub(lds, a.shared_off));
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
         LRA_TICK(9);
-        if (MODE == OUT_MEL2 && LRA_ABLATE != 12 && LRA_ABLATE != 13) {
+        if (MODE == OUT_MEL2) {
             LRA_PHASE(Cfg::NT, tid) {
                 const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
                 const Lds sl = lds_sub(lds, slot * slot_bytes);
@@ -1330,7 +1264,7 @@ template <class Cfg, int MODE, int PM = POW_TWO, int RAM = 0> LRA_HD void stft_b
             } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
         }
         if (MODE == OUT_MEL || MODE == OUT_MELR) {
-            if (MODE == OUT_MELR) lra_setprio<LRA_V1_PRIO_B3>();
+            if (MODE == OUT_MELR) lra_setprio<kV1PrioB3>();
             LRA_PHASE(Cfg::NT, tid) {
                 const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
                 const Lds sl = lds_sub(lds, slot * slot_bytes);
@@ -1410,10 +1344,7 @@ LRA_HD long long istft_written_end(int n_fft, int hop, long long n_used, int dro
 // register budget allows (the ascending-radix float configuration: n_fft = 2048) it lives in R - HC register pairs instead of LDS --
 // 2 (R - HC) LDS instructions per frame and thread less (24 of 54 at hop = n_fft / 4), for no instruction more: the frame's sums ARE
 // the next frame's carry, one hop of rows down.
-#ifndef LRA_ISTFT_REG_CARRY
-#define LRA_ISTFT_REG_CARRY 1
-#endif
-template <class Cfg, int HC> constexpr bool istft_reg_carry() { return LRA_ISTFT_REG_CARRY && HC > 0 && Cfg::REV && Cfg::HOIST && sizeof(typename Cfg::real) == 4 && Cfg::R == 16; }
+template <class Cfg, int HC> constexpr bool istft_reg_carry() { return HC > 0 && Cfg::REV && Cfg::HOIST && sizeof(typename Cfg::real) == 4 && Cfg::R == 16; }
 template <class Cfg, int HC = 0> constexpr int istft_carry_reals() { return istft_reg_carry<Cfg, HC>() ? 0 : (HC > 0 ? (Cfg::R - HC) * Cfg::TF * 2 : 2 * Cfg::N); }
 template <class Cfg, int HC = 0> constexpr int istft_slot_bytes() { return Cfg::FRAME_BYTES + ((istft_carry_reals<Cfg, HC>() * (int)sizeof(typename Cfg::real) + 15) / 16) * 16; }
 template <class Cfg, int HC = 0> constexpr int istft_lds_bytes() { return Cfg::FPB * istft_slot_bytes<Cfg, HC>(); }
@@ -2077,67 +2008,34 @@ template <class Cfg, int HC = 0> LRA_HD void istft_block(const IstftArgs<typenam
     } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
     for (int j = 0; j < steps; ++j) {
         if (!Cfg::HOIST) { LRA_LAUNDER(a.win_scaled); LRA_LAUNDER(a.tw); LRA_LAUNDER(a.twr); }
-        lra_setprio<LRA_I_PRIO_A>();   // wave priority per phase (s_setprio, -1 = none): A = un-split + loads + held-back stores, B = the passes + overlap-add
-        // (a) split the prefetched spectrum of frame j into LDS, (b) only now issue the held-back output
-        // stores of frame j-1, (c) start the prefetch of frame j+1: the wait in (a) never covers (b)
+        // (a) split the prefetched spectrum of frame j into LDS, (b) start the prefetch of frame j+1, (c) only now issue
+        // the held-back output stores of frame j-1: the wait in (a) never covers (c)
         LRA_PHASE(Cfg::NT, tid) {
             const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid);
             const IstftSlot<Cfg> s = LRA_R(sl);
             const int t = s.t0 - a.warm_frames + j;
-#if defined(__HIP_DEVICE_COMPILE__) && defined(LRA_ISTFT_ABLATE)
-            if constexpr ((LRA_ISTFT_ABLATE & 4) != 0 && sizeof(T) == 4) {  // (the experiment's load targets stay allocated while their loads are in flight)
-                LRA_UNROLL
-                for (int q = 0; q < Cfg::R; ++q) { LRA_KEEP(LRA_R(rg).nxt[q].x); LRA_KEEP(LRA_R(rg).nxt[q].y); }
-            }
-#endif
             if constexpr (MIR4) istft_unsplit_pass0_mir4<Cfg>(tf, LRA_R(rg), lds_sub(lds, slot * SB));
             else if constexpr (MIR) istft_unsplit_pass0<Cfg>(tf, LRA_R(rg), lds_sub(lds, slot * SB));
             else istft_split_write<Cfg>(a, tf, LRA_R(rg), lds_sub(lds, slot * SB));
-#ifndef LRA_ISTFT_ABLATE  // timing experiments (scripts/ab_run.sh): bit 0 = no spectrum loads in the frame loop, bit 1 = no output stores
-#define LRA_ISTFT_ABLATE 0
-#endif
-            const bool ablate_never = LRA_ISTFT_ABLATE != 0 && a.tiny == (T)12345.678;  // never true at run time
-#ifndef LRA_ISTFT_LOADS_FIRST
-#define LRA_ISTFT_LOADS_FIRST 1
-#endif
+            // the next frame's spectrum loads go out BEFORE the held-back stores: vector-memory operations retire in order, so loads
+            // queued behind stores are only seen complete once those stores have been acknowledged
+            // (kept as a lambda: spelled as a plain statement the same loads make hipcc pick other registers and another order in the n_fft = 1024 instances)
             auto prefetch = [&]() {
-                if (j + 1 < steps && (!(LRA_ISTFT_ABLATE & 1) || ablate_never)) {
+                if (j + 1 < steps) {
                     if constexpr (MIR4) istft_spec_load_mir4<Cfg>(a, s.clip, t + 1, s.active && t + 1 >= 0 && t + 1 < s.t1, tf, LRA_R(rg));
                     else if constexpr (MIR) istft_spec_load_mir<Cfg>(a, s.clip, t + 1, s.active && t + 1 >= 0 && t + 1 < s.t1, tf, LRA_R(rg));
                     else istft_spec_load<Cfg>(a, s.clip, t + 1, s.active && t + 1 >= 0 && t + 1 < s.t1, tf, LRA_R(rg));
                 }
             };
-            // the next frame's spectrum loads go out BEFORE the held-back stores: vector-memory operations retire in order, so loads
-            // queued behind stores are only seen complete once those stores have been acknowledged
-            if (LRA_ISTFT_LOADS_FIRST) prefetch();
-            if (defer && j > 0 && s.active && (!(LRA_ISTFT_ABLATE & 2) || ablate_never)) {
+            prefetch();
+            if (defer && j > 0 && s.active) {
                 if constexpr (rows) istft_flush_rows<Cfg, HC>(a, s.clip, t - 1, t - 1 >= s.t0 && (s.last || t - 1 < s.t1), tf, LRA_R(rg));
                 else istft_flush_out<Cfg>(a, s.clip, t - 1, s.write_lo, s.write_hi, tf, LRA_R(rg));
             }
-            if (!LRA_ISTFT_LOADS_FIRST) prefetch();
             if constexpr (rows) {  // for the flush of THIS frame, one iteration from now
-                if (s.active && (!(LRA_ISTFT_ABLATE & 8) || ablate_never)) istft_wss_rows<Cfg, HC>(a, s.clip, t, t >= s.t0 && (s.last || t < s.t1), tf, LRA_R(rg));
+                if (s.active) istft_wss_rows<Cfg, HC>(a, s.clip, t, t >= s.t0 && (s.last || t < s.t1), tf, LRA_R(rg));
             }
-#if defined(__HIP_DEVICE_COMPILE__) && (LRA_ISTFT_ABLATE & 4)
-            // experiment: the next frame's spectrum is read (16 loads the compiler does not know about, into registers nothing else uses) and never
-            // waited for -- what the read traffic costs the arithmetic when nothing waits on it
-            if constexpr (MIR && sizeof(T) == 4) {
-                if (j + 1 < steps && s.active && t + 1 >= 0 && t + 1 < s.t1) {
-                    const typename Cfg::cplx* X = a.D + s.clip * a.d_batch_stride + (long long)(t + 1) * a.d_frame_stride;
-                    LRA_UNROLL
-                    for (int q = 0; q < Cfg::R / 2; ++q) {
-                        const typename Cfg::cplx* pk = X + tf + q * 2 * Cfg::TF;
-                        const typename Cfg::cplx* pm = X + Cfg::M - tf - q * 2 * Cfg::TF;
-                        asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(LRA_R(rg).nxt[2 * q]) : "v"(pk));
-                        asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(LRA_R(rg).nxt[2 * q + 1]) : "v"(pm));
-                    }
-                }
-                LRA_UNROLL
-                for (int q = 0; q < Cfg::R; ++q) { LRA_KEEP(LRA_R(rg).nxt[q].x); LRA_KEEP(LRA_R(rg).nxt[q].y); }
-            }
-#endif
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-        lra_setprio<LRA_I_PRIO_B>();
         // pass 0 (no twiddles) reads from LDS here, unlike the forward kernel (unless it was fused into the Hermitian step)
         if (Cfg::P > 1 && !MIR) {
             LRA_PHASE(Cfg::NT, tid) {

@@ -42,52 +42,19 @@ template <class Cfg> LRA_HD int v2_hop_divisor(int hop) {
     return 0;
 }
 
-#ifndef LRA_V2_ROTATE_MEL
-#define LRA_V2_ROTATE_MEL 0  // the rotating register ring for the mel epilogue too (measured +1 % without wave priorities, see the frame loop)
-#endif
-// s_setprio at the phase boundaries of the frame loop (see there; lra_common.h, lra_setprio).  Mel kernel: A = window + transform passes (A1: the
-// passes apart from pass 0), S = un-split + power row, B / B2 / B3 = the epilogue's run read / accumulate / band combine; complex / power kernels:
-// CA = transform, CS = un-split + stores.  -1: no instruction.  Measured on the 256 x 30 s batch (same box, alternating; product without: 0.604 ms):
+// s_setprio at the phase boundaries of the frame loop (see there; lra_common.h, lra_setprio).  Mel kernel: A = window + transform passes,
+// S = un-split + power row, B / B3 = the epilogue's run read / band combine (the accumulate phase in between sets none); complex / power kernels:
+// CA = transform, CS = un-split + stores.  Measured on the 256 x 30 s batch (same box, alternating; product without: 0.604 ms):
 // 3 / 2 / 0 / combine 1: 0.564-0.568; 3 / 2 / 0: 0.570-0.574; 3 / 2 / 1: 0.570; 3 / 3 / 0: 0.573-0.576; 2 / 3 / 0: 0.578; 3 / 0 / 0: 0.603; the
 // reverse order (0 / - / 3): 0.583-0.587.  The store-bound complex kernel: CA 3 / CS 0 0.744 against 0.747 (left alone), the reverse 0.757.
-#ifndef LRA_V2_STAGGER_ALL
-#define LRA_V2_STAGGER_ALL 0
-#endif
-#ifndef LRA_V2_PRIO_A
-#define LRA_V2_PRIO_A 3
-#endif
-#ifndef LRA_V2_PRIO_S
-#define LRA_V2_PRIO_S 2
-#endif
-#ifndef LRA_V2_PRIO_B
-#define LRA_V2_PRIO_B 0
-#endif
-#ifndef LRA_V2_PRIO_B2
-#define LRA_V2_PRIO_B2 -1
-#endif
-#ifndef LRA_V2_PRIO_B3
-#define LRA_V2_PRIO_B3 1
-#endif
-#ifndef LRA_V2_PRIO_A1
-#define LRA_V2_PRIO_A1 -1
-#endif
+constexpr int kV2PrioA = 3, kV2PrioS = 2, kV2PrioB = 0, kV2PrioB3 = 1;
 // (round 5: 3 / 2 for the complex kernel too -- over seven allocations per process and two rounds its slow level reads 0.737-0.741 / 0.732-0.735 ms against
-// 0.742-0.746 / 0.739-0.745 without, profiles/r05_raw/aa_*: under 1 %, but the same sign every time; the inverse kernel's priorities (LRA_I_PRIO_*) move nothing)
-#ifndef LRA_V2_PRIO_CA
-#define LRA_V2_PRIO_CA 3
-#endif
+// 0.742-0.746 / 0.739-0.745 without, profiles/r05_raw/aa_*: under 1 %, but the same sign every time; priorities in the inverse kernel move nothing)
+constexpr int kV2PrioCA = 3, kV2PrioCS = 2;
 // |X|^p epilogue (round 5): PA = window + transform passes, PS = un-split + power stores.  Same box, alternating, 256 x 30 s:
 // none 0.518-0.521 ms, 3 / 2 0.499-0.501, 3 / 0 0.498-0.499 (profiles/r05_raw/z_prio_power.txt); the complex kernel with the same pair: inside its
 // allocation-to-allocation spread, left alone.
-#ifndef LRA_V2_PRIO_PA
-#define LRA_V2_PRIO_PA 3
-#endif
-#ifndef LRA_V2_PRIO_PS
-#define LRA_V2_PRIO_PS 2
-#endif
-#ifndef LRA_V2_PRIO_CS
-#define LRA_V2_PRIO_CS 2
-#endif
+constexpr int kV2PrioPA = 3, kV2PrioPS = 2;
 template <int P> LRA_HD void v2_setprio() { lra_setprio<P>(); }
 
 template <class Cfg, int HD> struct Regs2 {
@@ -215,15 +182,12 @@ template <class Cfg, int HD> LRA_HD void v2_shift(Regs2<Cfg, HD>& rg) {
     }
 }
 
-// The register ring WITHOUT the shift (LRA_V2_ROTATE): the R pairs stay where they are and the frame's VIEW of them rotates.  Logical
+// The register ring WITHOUT the shift: the R pairs stay where they are and the frame's VIEW of them rotates.  Logical
 // pass-0 row j of the slot's frame number `it` lives in physical row (j + SJ it) mod r0, so the only data that moves per frame are the
 // SJ new rows per butterfly (R / HD pairs: 4 at hop = n_fft / 4) from their landing registers into the rows the previous frame read
 // first; the window multiply picks its operands by the rotation, which is wave-uniform (a scalar switch with HD arms of R packed
 // multiplies each -- the rest of the frame is rotation-free).  v2_shift moved all R pairs every frame: 16 v_mov_b64 at n_fft = 2048
 // (+ the copies hipcc adds at the loop's back edge), 3.4 % of the kernel by ablation (profiles/r03_experiments.md section 1).
-#ifndef LRA_V2_ROTATE
-#define LRA_V2_ROTATE 1
-#endif
 // The C++ spelling of the rotating view (what the host simulator runs, and the definition of the assembly below).
 template <class Cfg, int HD> LRA_HD void v2_window_rotating_ref(int it, Regs2<Cfg, HD>& rg) {
     using T = typename Cfg::real;
@@ -240,7 +204,7 @@ template <class Cfg, int HD> LRA_HD void v2_window_rotating_ref(int it, Regs2<Cf
     }
 }
 template <class Cfg, int HD> constexpr bool v2_rotate_asm_ok() {
-    return LRA_V2_ROTATE && HD == 4 && Regs2<Cfg, HD>::r0 == 16 && Regs2<Cfg, HD>::nb0 == 1 && sizeof(typename Cfg::real) == 4;
+    return HD == 4 && Regs2<Cfg, HD>::r0 == 16 && Regs2<Cfg, HD>::nb0 == 1 && sizeof(typename Cfg::real) == 4;
 }
 #if defined(LRA_PK_ASM)
 // One residue class of rows (c, c + 4, c + 8, c + 12: the rows a frame's hop of four rows maps onto each other), n_fft / hop = 4, sixteen rows:
@@ -348,25 +312,17 @@ template <class Cfg, int HD> LRA_HD void v2_last_read(Regs2<Cfg, HD>& rg, Lds fr
 }
 
 
-// staged complex epilogue (v2_store_row below): 16-byte pieces, and where a row starts relative to them
+// 16-byte pieces
 template <class T> struct alignas(16) V4 {
     T a, b, c, d;
 };
-template <class Cfg> LRA_HD int v2_row_shift(const StftArgs<typename Cfg::real>& a, int clip, int frame) {
-    const long long row = ((long long)clip * a.n_frames + frame) * a.row_pitch;
-    return (int)(reinterpret_cast<size_t>(a.D + row) & (2 * sizeof(typename Cfg::real)));  // 0 or sizeof(cplx): the row starts on / half-way into a 16-byte piece
-}
-
 // OUT_MELR: float index of bin k in the power row.  Runs of 8 bins back to back, the two 16-byte halves of a run swapped where bit 7 of the
 // bin is set: the butterfly-order writes (lanes = 32 consecutive bins, ds_write_b32) then stay within a handful of distinct banks per
 // lane group, and the run reads (ds_read_b128, thread tf takes run tf: sixteen lanes 32 bytes apart) find the halves of neighbouring
 // lane groups on disjoint bank quarters.  scripts/lds_model.py: 36 + 16 LDS cycles per frame for the 16 writes + 4 reads against 64 + 16
 // for the round-3 layout (runs 48 bytes apart, every 32-lane write 2-way conflicted).  Linear over steps of 256 bins: idx(k + 256) = idx(k) + 256.
-#ifndef LRA_MEL_PW_SWZ
-#define LRA_MEL_PW_SWZ 1
-#endif
 // (the swizzled form needs pair slots a whole number of 128-bin blocks apart: n_fft >= 2048 at sixteen points per thread; smaller frames keep the padded runs)
-template <class Cfg> constexpr bool v2_pw_swz() { return LRA_MEL_PW_SWZ && (2 * Cfg::TF) % 128 == 0; }
+template <class Cfg> constexpr bool v2_pw_swz() { return (2 * Cfg::TF) % 128 == 0; }
 template <bool SWZ> LRA_HD int v2_pw_index_t(int k) {
     if (SWZ) return (k >> 3) * 8 + ((((k >> 2) ^ (k >> 7)) & 1) << 2) + (k & 3);
     return (k >> 3) * 12 + (k & 7);
@@ -401,7 +357,7 @@ template <class Cfg> LRA_HD void v2_pw_addr_xor(Lds stage, int tf, int tfh, bool
 }
 
 // phase: last-pass butterflies, Hermitian split in registers, epilogue (complex spectrum or |X|^power) to HBM
-template <class Cfg, int HD, int MODE, int PM, bool STAGED, bool PIN = true>
+template <class Cfg, int HD, int MODE, int PM, bool PIN = true>
 LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip, int frame, bool valid, int tf, Regs2<Cfg, HD>& rg, Lds stage) {
     using T = typename Cfg::real;
     using C = typename Cfg::cplx;
@@ -416,7 +372,6 @@ LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
     const long long row = ((long long)clip * a.n_frames + frame) * a.row_pitch;
     C* __restrict__ const D = MODE == OUT_COMPLEX ? a.D + row : nullptr;
     T* __restrict__ const S = MODE == OUT_POWER ? a.S + row : nullptr;
-    const int sh = (MODE == OUT_COMPLEX && STAGED) ? v2_row_shift<Cfg>(a, clip, frame) : 0;
     // OUT_MELR: byte addresses of the power-row slots of this thread's four bin families (k = tf + q s and M - k, with lane 0's
     // alternative bases), pinned in registers: left to itself hipcc re-derives (k >> 3) * 12 + (k & 7) for each of the 16 stores
     // (4 VALU instructions each) rather than keep four values live
@@ -480,19 +435,8 @@ LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
                 lds_st<T>(stage, pwk[q < r / 2 ? 0 : 1][0] + 24 * q * (s / 16) * (int)sizeof(T), vk);
                 lds_st<T>(stage, pwm[q < r / 2 ? 0 : 1][0] - 24 * q * (s / 16) * (int)sizeof(T), vm);
             }
-        } else if (MODE == OUT_COMPLEX && STAGED) {
-            // the row goes to LDS in bin order (the frame area is free: every Z is in registers), shifted so that LDS and
-            // global addresses agree modulo 16; v2_store_row then writes it as aligned 16-byte pieces.  Of the two bins that
-            // a row of 1025 has in excess of whole 16-byte pieces one is stored here: bin 0 or bin M, both lane 0's slot 0.
-            lds_st<C>(stage, sh + k * (int)sizeof(C), xk);
-            lds_st<C>(stage, sh + (M - k) * (int)sizeof(C), xm);
-            if (q == 0 && l0 && valid) D[sh ? 0 : M] = sh ? xk : xm;
         } else if (MODE == OUT_COMPLEX) {
-#if LRA_ABLATE == 1
-            if (valid && xk.x == (T)12345.678) { stream_store(&D[k], xk); stream_store(&D[M - k], xm); }
-#else
             if (valid) { stream_store(&D[k], xk); stream_store(&D[M - k], xm); }
-#endif
         } else {
             const T pk = spec_power<T, PM>(xk, a.power), pm = spec_power<T, PM>(xm, a.power);
             if (valid) { S[k] = pk; S[M - k] = pm; }
@@ -503,36 +447,9 @@ LRA_HD void v2_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
     const C xmid = mk<T>((T)2 * zmid.x, (T)-2 * zmid.y);
     if (MODE == OUT_MELR) {
         if (l0) lds_st<T>(stage, v2_pw_index<Cfg>(M / 2) * (int)sizeof(T), spec_power<T, PM>(xmid, a.power));
-    } else if (MODE == OUT_COMPLEX && STAGED) {
-        if (l0) lds_st<C>(stage, sh + (M / 2) * (int)sizeof(C), xmid);
     } else if (l0 && valid) {
         if (MODE == OUT_COMPLEX) D[M / 2] = xmid;
         else S[M / 2] = spec_power<T, PM>(xmid, a.power);
-    }
-}
-
-// Staged complex epilogue, second half: the row sits in LDS (v2_last_split_store) and leaves as whole 16-byte pieces:
-// 8 M bytes = M / (2 TF) store instructions of TF x 16 contiguous bytes each, starting at the row's first 16-byte
-// boundary.  Measured on the bare store stream (scripts/storepat2.hip): 8-byte pieces in butterfly order 5.0 TB/s,
-// aligned 16-byte pieces 5.4, and only these take non-temporal stores and the XCD-aware workgroup map well (6.2).
-template <class Cfg> LRA_HD void v2_store_row(const StftArgs<typename Cfg::real>& a, int clip, int frame, bool valid, int tf, Lds stage) {
-    using T = typename Cfg::real;
-    using C = typename Cfg::cplx;
-    constexpr int M = Cfg::M, PIECES = M / (2 * Cfg::TF);
-    static_assert(sizeof(T) == 4, "16-byte pieces of complex64");
-    if (!valid) return;
-    const long long row = ((long long)clip * a.n_frames + frame) * a.row_pitch;
-    const int sh = v2_row_shift<Cfg>(a, clip, frame);
-    char* __restrict__ const g = reinterpret_cast<char*>(a.D + row) + sh + 16 * tf;  // first aligned piece of this thread
-    V4<T> w[PIECES];
-    LRA_UNROLL
-    for (int c = 0; c < PIECES; ++c) w[c] = lds_ld<V4<T>>(stage, 2 * sh + c * 16 * Cfg::TF + 16 * tf);
-    LRA_UNROLL
-    for (int c = 0; c < PIECES; ++c) {
-#if LRA_ABLATE == 1  // experiment: everything but the spectrum stores
-        if (w[c].a != (T)12345.678) continue;
-#endif
-        stream_store16(reinterpret_cast<V4<T>*>(g + c * 16 * Cfg::TF), w[c]);
     }
 }
 
@@ -609,9 +526,6 @@ template <class Cfg, int HD> LRA_HD void v2_mel_accumulate(const StftArgs<typena
 // 114 butterfly instructions against 112).
 // LDS hand-over middle pass -> last pass: element i at slot i + 16 (i >> 8) (blocks of 256 + 16 slots): the middle pass's stores (lanes 16 a + k
 // -> 256 a + k + 16 j) are conflict-free, the last pass reads (E, O)[j] as ONE aligned 16-byte piece at 16 t + 2176 j, Om / Em as 8-byte reads.
-#ifndef LRA_V3_DERIVE_TWR
-#define LRA_V3_DERIVE_TWR 1
-#endif
 template <class Cfg> constexpr bool v3_cfg_ok() {
     return Cfg::PLAN == 1 && Cfg::P == 3 && Cfg::R == 16 && Cfg::HOIST && sizeof(typename Cfg::real) == 4 && Cfg::logr(0) == 4 && Cfg::logr(1) == 4 && Cfg::logr(2) == 2 &&
            Cfg::TF == 64 && affine_tf<Cfg>();
@@ -650,7 +564,7 @@ template <class Cfg, int HD> LRA_HD void v3_hoist(Regs2<Cfg, HD>& rg, int tf, co
     // (the O slots' twiddles W_N^(2 tf + 1 + j s), j = 1 .. 3, are W_N^(2 tf + 1) times e^(-i pi j / 4): three or four instructions per frame in
     // v3_last_split_store instead of six registers -- with all eight held the complex kernel needs 174 VGPRs, six more than three waves per SIMD allow)
     LRA_UNROLL
-    for (int q = 0; q < (LRA_V3_DERIVE_TWR ? 5 : 8); ++q) rg.twr[q] = twr_full[v3_slot_bin<Cfg>(tf, q)];
+    for (int q = 0; q < 5; ++q) rg.twr[q] = twr_full[v3_slot_bin<Cfg>(tf, q)];
 }
 // middle pass twiddles, register-lean.  pass_twiddle_dft_reg derives all fifteen W^(k j) from the four stored powers first (w[16] + q[16] live next to
 // v[16]: the complex kernel then needs ~206 VGPRs and spills 38 under the three-wave budget).  Here W^(k (8 + j)) v = W^(k j) (W^(8 k) v): the upper eight
@@ -723,9 +637,6 @@ template <class Cfg, int HD> LRA_HD void v3_last_read(Regs2<Cfg, HD>& rg, Lds fr
     }
 }
 // two neighbouring elements as one store (global_store_dwordx4 / dwordx2: the pointer need only be element-aligned)
-#ifndef LRA_V3_NT
-#define LRA_V3_NT 0  // non-temporal 16-byte row pieces (experiment)
-#endif
 template <class V> LRA_HD void store_pair(V* p, V lo, V hi) {
 #if !defined(LRA_HOSTSIM)
     if constexpr (sizeof(V) == 8) {
@@ -733,11 +644,7 @@ template <class V> LRA_HD void store_pair(V* p, V lo, V hi) {
         const cx<float> l = __builtin_bit_cast(cx<float>, lo), h = __builtin_bit_cast(cx<float>, hi);
         f4u v;
         v.x = l.x; v.y = l.y; v.z = h.x; v.w = h.y;
-#if LRA_V3_NT
-        __builtin_nontemporal_store(v, reinterpret_cast<f4u*>(p));
-#else
         *reinterpret_cast<f4u*>(p) = v;
-#endif
         return;
     } else if constexpr (sizeof(V) == 4) {
         typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -787,8 +694,8 @@ LRA_HD void v3_last_split_store(const StftArgs<typename Cfg::real>& a, int clip,
     for (int jo = 0; jo < 4; ++jo) {
         const int j = jo == 0 ? 1 : (jo == 1 ? 0 : jo);  // 1, 0, 2, 3
         C xkO, xmO, xkE, xmE;
-        C wO = rg.twr[LRA_V3_DERIVE_TWR ? 4 : 4 + j];
-        if (LRA_V3_DERIVE_TWR && j > 0) {
+        C wO = rg.twr[4];
+        if (j > 0) {
             const T h = (T)0.70710678118654752440;
             const C t = rg.twr[4];
             if (j == 1) { const C u = add_mi(t, t); wO = mk<T>(h * u.x, h * u.y); }          // e^(-i pi / 4) = h (1 - i)
@@ -870,7 +777,7 @@ template <class Cfg> constexpr int stft2_slot_bytes() { return Cfg::FRAME_BYTES;
 template <class Cfg, int HD, int MODE, int PM = POW_TWO> LRA_HD void stft_block2(const StftArgs<typename Cfg::real>& a_in, const int blk, Lds lds) {
     static_assert(v23_cfg_ok<Cfg>(), "configuration has no mirrored last pass");
     static_assert(MODE == OUT_COMPLEX || MODE == OUT_POWER || MODE == OUT_MELR, "epilogues of the second-generation kernel");
-    static_assert(MODE != OUT_MELR || (melr_fits<Cfg>() && v2_pw_bytes<Cfg>() <= Cfg::FRAME_BYTES && (Cfg::R * (Cfg::TF + LRA_MEL_RS_PITCH_EXTRA) + 2) * 2 * (int)sizeof(typename Cfg::real) <= Cfg::FRAME_BYTES),
+    static_assert(MODE != OUT_MELR || (melr_fits<Cfg>() && v2_pw_bytes<Cfg>() <= Cfg::FRAME_BYTES && (Cfg::R * (Cfg::TF + kMelRsPitchExtra) + 2) * 2 * (int)sizeof(typename Cfg::real) <= Cfg::FRAME_BYTES),
                   "mel epilogue: running sums (pitch TF + 1) and power row live in the frame area");
     StftArgs<typename Cfg::real> a = a_in;
     using RG = Regs2<Cfg, HD>;
@@ -878,15 +785,8 @@ template <class Cfg, int HD, int MODE, int PM = POW_TWO> LRA_HD void stft_block2
     const int f_first = (blk % a.wg_per_clip) * a.frames_per_wg;
     const int iters = a.frames_per_wg / Cfg::FPB;
     constexpr int SB = stft2_slot_bytes<Cfg>();
-    // Complex epilogue form.  0 (product): 8-byte stores straight from the butterfly registers.  1 (experiment): the row is
-    // staged in LDS and leaves as aligned 16-byte pieces (v2_store_row).  On the bare store stream aligned pieces are up to
-    // 6 % faster, but a kernel with 12 resident waves per CU is bound by the bytes it keeps in flight, not by the piece
-    // size: measured 0.66 ms direct vs 0.72-0.74 ms staged (with or without non-temporal stores) for the 256 x 30 s batch,
-    // the staging round trip costing more LDS time than the wider stores save (profiles/r02_store_stream.md).
-#ifndef LRA_V2_STAGED
-#define LRA_V2_STAGED 0
-#endif
-    constexpr bool STAGED = Cfg::PLAN == 0 && MODE == OUT_COMPLEX && LRA_V2_STAGED && sizeof(typename Cfg::real) == 4 && (Cfg::M + 3) * (int)sizeof(typename Cfg::cplx) <= SB;
+    // Complex epilogue: 8-byte stores straight from the butterfly registers.  Staging the row in LDS so that it leaves as aligned
+    // 16-byte pieces measured 0.72-0.74 ms against 0.66 ms direct for the 256 x 30 s batch (profiles/r02_store_stream.md).
     LRA_REGS(RG, rg, Cfg::NT);
     LRA_PHASE(Cfg::NT, tid) {
         const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid);
@@ -907,26 +807,17 @@ template <class Cfg, int HD, int MODE, int PM = POW_TWO> LRA_HD void stft_block2
             melr_hoist<Cfg>(a, tf, LRA_R(rg), slot * SB);  // (addresses relative to the workgroup's LDS, not to the slot)
         }
     } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC && MODE != OUT_MELR)  // the shared mel tables need a workgroup barrier, once
-#if defined(LRA_V2_STAGGER) && !defined(LRA_HOSTSIM)
-    // experiment (round 5): the two waves that share a SIMD start LRA_V2_STAGGER x 64 cycles apart -- the wave in an odd
-    // hardware wave slot sleeps before its first frame (HW_ID bits 3:0 = wave slot within the SIMD) -- instead of drifting there over the first frames
-    if (MODE == OUT_MELR || LRA_V2_STAGGER_ALL) {
-        unsigned hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        if (hw & 1u) __builtin_amdgcn_s_sleep(LRA_V2_STAGGER);
-    }
-#endif
     for (int it = 0; it < iters; ++it) {
         if (f_first + it >= a.n_frames) break;  // slot 0 has the smallest frame index: uniform exit
-        // Wave priority per phase (s_setprio; LRA_V2_PRIO_A: window + transform passes, _S: un-split + stores / power row, _B: mel epilogue;
-        // -1 = leave alone).  profiles/r04_experiments.md 10.
-        v2_setprio<MODE == OUT_MELR ? LRA_V2_PRIO_A : (MODE == OUT_POWER ? LRA_V2_PRIO_PA : LRA_V2_PRIO_CA)>();
+        // Wave priority per phase (s_setprio; A: window + transform passes, S: un-split + stores / power row, B: mel epilogue).
+        // profiles/r04_experiments.md 10.
+        v2_setprio<MODE == OUT_MELR ? kV2PrioA : (MODE == OUT_POWER ? kV2PrioPA : kV2PrioCA)>();
         LRA_PHASE(Cfg::NT, tid) {
             const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
             RG& r = LRA_R(rg);
             // (measured, profiles/r04_experiments.md: 21 vector instructions per frame fewer and the same time for the complex / power
             // epilogues; 1 % SLOWER with the mel epilogue, whose issue-bound loop pays for the switches' taken branches -- it keeps the shift)
-            if (v2_rotate_asm_ok<Cfg, HD>() && (MODE != OUT_MELR || LRA_V2_ROTATE_MEL)) {
+            if (v2_rotate_asm_ok<Cfg, HD>() && MODE != OUT_MELR) {
                 v2_window_rotating<Cfg, HD>(it, r);                                      // consumes the pairs loaded during the previous frame (4 moves, not 16)
                 if (it + 1 < iters) v2_issue_loads<Cfg, HD>(a, clip, frame + 1, tf, r);  // ... and starts the next batch, BEFORE this frame's stores
                 v2_pass0_dft<Cfg, HD>(tf, r, lds_sub(lds, slot * SB));
@@ -936,7 +827,6 @@ template <class Cfg, int HD, int MODE, int PM = POW_TWO> LRA_HD void stft_block2
                 v2_pass0<Cfg, HD>(frame < a.n_frames, tf, r, lds_sub(lds, slot * SB));
             }
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-        if (MODE == OUT_MELR) v2_setprio<LRA_V2_PRIO_A1>();   // (middle + last passes apart from window / pass 0)
 #define LRA_MID_PASS2(p)                                                                                                  \
         if (Cfg::P - 1 > p) {                                                                                             \
             LRA_PHASE(Cfg::NT, tid) {                                                                                     \
@@ -958,50 +848,31 @@ template <class Cfg, int HD, int MODE, int PM = POW_TWO> LRA_HD void stft_block2
         LRA_PHASE(Cfg::NT, tid) {
             if constexpr (Cfg::PLAN == 1) v3_last_read<Cfg, HD>(LRA_R(rg), lds_sub(lds, slot_of<Cfg>(tid) * SB), lane_of<Cfg>(tid));
             else v2_last_read<Cfg, HD>(LRA_R(rg), lds_sub(lds, slot_of<Cfg>(tid) * SB), lane_of<Cfg>(tid));
-        } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC || (LRA_SPLIT_ONE_BARRIER && MODE != OUT_MELR && !STAGED))  // (registers -> HBM next: see stft_block)
-        v2_setprio<MODE == OUT_MELR ? LRA_V2_PRIO_S : (MODE == OUT_POWER ? LRA_V2_PRIO_PS : LRA_V2_PRIO_CS)>();
+        } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC || MODE != OUT_MELR)  // (registers -> HBM next: see stft_block)
+        v2_setprio<MODE == OUT_MELR ? kV2PrioS : (MODE == OUT_POWER ? kV2PrioPS : kV2PrioCS)>();
         LRA_PHASE(Cfg::NT, tid) {
             const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
             if constexpr (Cfg::PLAN == 1) v3_last_split_store<Cfg, HD, MODE, PM>(a, clip, frame, frame < a.n_frames, tf, LRA_R(rg), lds_sub(lds, slot * SB));
-            else v2_last_split_store<Cfg, HD, MODE, PM, STAGED>(a, clip, frame, frame < a.n_frames, tf, LRA_R(rg), lds_sub(lds, slot * SB));
+            else v2_last_split_store<Cfg, HD, MODE, PM>(a, clip, frame, frame < a.n_frames, tf, LRA_R(rg), lds_sub(lds, slot * SB));
         } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-        if (STAGED) {
-            LRA_PHASE(Cfg::NT, tid) {
-                const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
-                v2_store_row<Cfg>(a, clip, frame, frame < a.n_frames, tf, lds_sub(lds, slot * SB));
-            } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-        }
         if (MODE == OUT_MELR) {
-            v2_setprio<LRA_V2_PRIO_B>();
+            v2_setprio<kV2PrioB>();
             // power row -> runs in registers; then (only then: the running sums reuse the row's bytes) weights, running sums
             // -> rs; then every band adds its piece totals (melr_combine, shared with the first-generation kernel)
-            // LRA_MEL_ABLATE = n (timing experiments, scripts/ab_run.sh): the last n of the three epilogue phases sit behind a
-            // condition that is never true at run time, so the code, its registers and everything upstream stay as they are
-#ifndef LRA_MEL_ABLATE
-#define LRA_MEL_ABLATE 0
-#endif
-            const bool ablate_never = LRA_MEL_ABLATE > 0 && a.power == (typename Cfg::real)12345.678;
-            if (LRA_MEL_ABLATE < 3 || ablate_never) {
             LRA_PHASE(Cfg::NT, tid) {
                 v2_mel_runs_read<Cfg, HD>(LRA_R(rg), lds_sub(lds, slot_of<Cfg>(tid) * SB), lane_of<Cfg>(tid));
                 v2_mel_weights_read<Cfg, HD>(LRA_R(rg), lds_sub(lds, a.shared_off), lane_of<Cfg>(tid));
             } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-            }
-            v2_setprio<LRA_V2_PRIO_B2>();
-            if (LRA_MEL_ABLATE < 2 || ablate_never) {
             LRA_PHASE(Cfg::NT, tid) {
                 v2_mel_accumulate<Cfg, HD>(a, lane_of<Cfg>(tid), LRA_R(rg), lds_sub(lds, slot_of<Cfg>(tid) * SB), lds_sub(lds, a.shared_off));
             } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-            }
-            v2_setprio<LRA_V2_PRIO_B3>();
-            if (LRA_MEL_ABLATE < 1 || ablate_never) {
+            v2_setprio<kV2PrioB3>();
             LRA_PHASE(Cfg::NT, tid) {
                 const int slot = slot_of<Cfg>(tid), tf = lane_of<Cfg>(tid), frame = f_first + slot * iters + it;
                 const Lds sl = lds_sub(lds, slot * SB);
                 if (frame < a.n_frames)
                     melr_combine<Cfg>(a, clip, frame, tf, it, 1, it + 1 == iters || frame + 1 >= a.n_frames, LRA_R(rg), lds_sub(lds, a.shared_off), sl, sl, lds);
             } LRA_PHASE_END_SYNC(Cfg::WAVE_SYNC)
-            }
         }
     }
 }

@@ -26,24 +26,11 @@
 
 namespace lra {
 
-#ifndef LRA_PC_PRIO_PA   // producer: window + transform passes
-#define LRA_PC_PRIO_PA 3
-#endif
-#ifndef LRA_PC_PRIO_PS   // producer: un-split + power row
-#define LRA_PC_PRIO_PS 2
-#endif
-#ifndef LRA_PC_PRIO_CA   // consumer: run read + accumulate
-#define LRA_PC_PRIO_CA 0
-#endif
-#ifndef LRA_PC_PRIO_CB   // consumer: band combine + bursts
-#define LRA_PC_PRIO_CB 1
-#endif
-#ifndef LRA_PC_ROTATE    // producer's register ring: 1 = rotating view (the complex kernel's form), 0 = shifted every frame (the mel kernel's form)
-#define LRA_PC_ROTATE 1
-#endif
-#ifndef LRA_PC_SPIN_LIMIT
-#define LRA_PC_SPIN_LIMIT (1 << 22)
-#endif
+// wave priorities (lra_setprio).  Producer: PA = window + transform passes, PS = un-split + power row; consumer: CA = run read + accumulate,
+// CB = band combine + bursts
+constexpr int kPcPrioPA = 3, kPcPrioPS = 2, kPcPrioCA = 0, kPcPrioCB = 1;
+constexpr int kPcSpinLimit = 1 << 22;  // polls of one flag before a wait gives up (and says so in the sticky flag)
+// (the producer's register ring is the rotating view wherever the configuration has one -- the complex kernel's form -- and shifted every frame elsewhere)
 
 template <class Cfg> struct PcLayout {
     using T = typename Cfg::real;
@@ -51,7 +38,7 @@ template <class Cfg> struct PcLayout {
     static constexpr int NT = (NP + 1) * Cfg::TF;    // 192 threads at one wave per frame
     static constexpr int FRAME = Cfg::FRAME_BYTES;
     static constexpr int PW = (v2_pw_bytes<Cfg>() + 15) / 16 * 16;                                                       // one power row
-    static constexpr int RS = ((Cfg::R * (Cfg::TF + LRA_MEL_RS_PITCH_EXTRA) + 2) * 2 * (int)sizeof(T) + 15) / 16 * 16;     // running sums + zero slot + extra bin's slot
+    static constexpr int RS = ((Cfg::R * (Cfg::TF + kMelRsPitchExtra) + 2) * 2 * (int)sizeof(T) + 15) / 16 * 16;     // running sums + zero slot + extra bin's slot
     static constexpr int frame_off(int s) { return s * FRAME; }
     static constexpr int pw_off(int s) { return NP * FRAME + s * PW; }
     static constexpr int rs_off() { return NP * (FRAME + PW); }
@@ -108,7 +95,7 @@ template <class Cfg> struct PcRegs {
 // (n_frames a multiple of 4; bands 2 tf, 2 tf + 1 have the same parity for every lane) it is one value per wave, producer slot and band
 // slot: the consumer then keeps it in a scalar register, picks the tile register by a scalar branch and takes the burst branch on a scalar
 // condition.  Otherwise every lane has its own slot (a select per tile register).  One branch per launch picks the form.
-template <class Cfg> LRA_HD bool pc_tile_uniform(const StftArgs<typename Cfg::real>& a) { return !LRA_MEL_ALIGNED_BURSTS || ((a.n_frames & 3) == 0 && Cfg::TF >= 64); }
+template <class Cfg> LRA_HD bool pc_tile_uniform(const StftArgs<typename Cfg::real>& a) { return (a.n_frames & 3) == 0 && Cfg::TF >= 64; }
 // piece-total pair at a hoisted address (rg.mad).  On the device the address is the absolute 32-bit LDS address, taken out of the compiler's
 // sight once in the prologue: as a symbol-relative offset the base add was sunk next to each of the sixteen reads, inside the frame loop.
 #ifdef LRA_HOSTSIM
@@ -154,7 +141,7 @@ __device__ __forceinline__ void pc_wait(Lds l, int off, int want, unsigned int* 
     while (true) {
         const int v = LRA_UNIFORM(pc_flag_load(l, off));
         if (LRA_LIKELY(v >= want)) break;
-        if (LRA_UNLIKELY(++spins > LRA_PC_SPIN_LIMIT)) {
+        if (LRA_UNLIKELY(++spins > kPcSpinLimit)) {
             if (sticky && (threadIdx.x & 63) == 0) atomicOr(sticky, 2u);
             break;
         }
@@ -175,7 +162,7 @@ template <class Cfg, int HD> LRA_HD void pc_producer_prologue(const StftArgs<typ
     if constexpr (Cfg::PLAN == 1) v3_hoist<Cfg, HD>(rg, tf, a.win, a.tw, a.twr);  // (radices 16, 16, 4: lra_kernels2.h, third form)
     else v2_hoist<Cfg, HD>(rg, tf, a.win, a.tw, a.twr);
     v2_fill<Cfg, HD>(a, clip, frame0, tf, rg);
-    if constexpr (v2_rotate_asm_ok<Cfg, HD>() && LRA_PC_ROTATE) {
+    if constexpr (v2_rotate_asm_ok<Cfg, HD>()) {
         LRA_UNROLL
         for (int e = 0; e < Cfg::R; ++e) { LRA_KEEP(rg.raw[e].x); LRA_KEEP(rg.raw[e].y); }  // (the fill's loads are waited for once, here: see stft_block2)
     }
@@ -184,7 +171,7 @@ template <class Cfg, int HD> LRA_HD void pc_producer_prologue(const StftArgs<typ
 }
 // window + pass-0 butterflies + first LDS write of frame `frame` (the slot's frame number `it`); starts the next frame's sample loads
 template <class Cfg, int HD> LRA_HD void pc_producer_pass0(const StftArgs<typename Cfg::real>& a, int clip, int frame, int it, bool more, int tf, Regs2<Cfg, HD>& rg, Lds fr) {
-    if (v2_rotate_asm_ok<Cfg, HD>() && LRA_PC_ROTATE) {
+    if (v2_rotate_asm_ok<Cfg, HD>()) {
         v2_window_rotating<Cfg, HD>(it, rg);
         if (more) v2_issue_loads<Cfg, HD>(a, clip, frame + 1, tf, rg);
         v2_pass0_dft<Cfg, HD>(tf, rg, fr);
@@ -211,7 +198,7 @@ template <class Cfg, int HD> LRA_HD void pc_last_read(Regs2<Cfg, HD>& rg, Lds fr
 }
 template <class Cfg, int HD, int PM> LRA_HD void pc_last_power_row(const StftArgs<typename Cfg::real>& a, int clip, int frame, int tf, Regs2<Cfg, HD>& rg, Lds pwr) {
     if constexpr (Cfg::PLAN == 1) v3_last_split_store<Cfg, HD, OUT_MELR, PM, false>(a, clip, frame, frame < a.n_frames, tf, rg, pwr);
-    else v2_last_split_store<Cfg, HD, OUT_MELR, PM, false, false>(a, clip, frame, frame < a.n_frames, tf, rg, pwr);
+    else v2_last_split_store<Cfg, HD, OUT_MELR, PM, false>(a, clip, frame, frame < a.n_frames, tf, rg, pwr);
 }
 
 // ---- consumer --------------------------------------------------------------------------------------------------------------------
@@ -259,7 +246,7 @@ template <class Cfg> LRA_HD void pc_consumer_prologue(const StftArgs<typename Cf
         LRA_UNROLL
         for (int b = 0; b < RG::NB; ++b) {
             // (as melr_tile_slot's scalar form at frame f_first + s iters; used only where pc_tile_uniform holds)
-            rg.ph[s][b] = LRA_MEL_ALIGNED_BURSTS ? (int)(((long long)clip * a.n_mels * a.n_frames + (long long)b * a.n_frames + f_first + s * iters) & (RG::TILE - 1)) : 0;
+            rg.ph[s][b] = (int)(((long long)clip * a.n_mels * a.n_frames + (long long)b * a.n_frames + f_first + s * iters) & (RG::TILE - 1));
             LRA_UNROLL
             for (int k = 0; k < RG::TILE; ++k) rg.mt[s][RG::TILE * b + k] = (T)0;
         }
@@ -363,7 +350,7 @@ template <class Cfg, bool UNI> __device__ __forceinline__ void pc_consumer(const
 #define LRA_PC_SERVE(S)                                                                                                        \
         {                                                                                                                      \
             const int frame = f_first + S * iters + it;                                                                       \
-            v2_setprio<LRA_PC_PRIO_CA>();                                                                                      \
+            v2_setprio<kPcPrioCA>();                                                                                      \
             pc_wait_ready(lds, L::ready_off(S), it + 1, a.nonfinite_flag);                                                     \
             pc_runs_read<Cfg>(rg, lds_sub(lds, L::pw_off(S)));                                                                 \
             pc_fence();                                                                                                        \
@@ -371,7 +358,7 @@ template <class Cfg, bool UNI> __device__ __forceinline__ void pc_consumer(const
             pc_fence();                                                                                                        \
             pc_accumulate<Cfg>(a, tf, rg, rs);                                                                                 \
             pc_fence();                                                                                                        \
-            v2_setprio<LRA_PC_PRIO_CB>();                                                                                      \
+            v2_setprio<kPcPrioCB>();                                                                                      \
             if (frame < a.n_frames) rg.mt[S] = pc_combine<Cfg, S, UNI>(a, clip, frame, tf, it, it + 1 == iters || frame + 1 >= a.n_frames, rg, lds, rg.mt[S]); \
             pc_fence();                                                                                                        \
         }
@@ -471,7 +458,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
         pc_fence();
         for (int it = 0; it < n_it; ++it) {
             const int frame = f_first + wave * iters + it;
-            v2_setprio<LRA_PC_PRIO_PA>();
+            v2_setprio<kPcPrioPA>();
             {
                 const int tf = (phase_tid() & (TF - 1));
                 pc_producer_pass0<Cfg, HD>(a, clip, frame, it, it + 1 < iters, tf, rg, fr);
@@ -494,7 +481,7 @@ template <class Cfg, int HD, int PM = POW_TWO> LRA_HD void stft_pc_block(const S
                 taken = pc_flag_load(lds, L::consumed_off(wave));  // rides on the same wait as the last pass's inputs
             }
             pc_fence();
-            v2_setprio<LRA_PC_PRIO_PS>();
+            v2_setprio<kPcPrioPS>();
             if (LRA_UNLIKELY(LRA_UNIFORM(taken) < it)) pc_wait(lds, L::consumed_off(wave), it, a.nonfinite_flag);  // row it - 1 still unread (it was handed over a whole frame ago)
             {
                 const int tf = (phase_tid() & (TF - 1));

@@ -24,24 +24,7 @@
 #include <hip/hip_runtime.h>
 #endif
 
-// wave priority per stage (s_setprio; experiment switch, profiles/r04_experiments.md 10): L = frame loads, P = passes, S = split, E = mel reduce; -1 = none
-#ifndef LRA_MIXED_PRIO_L
-#define LRA_MIXED_PRIO_L -1
-#endif
-#ifndef LRA_MIXED_PRIO_P
-#define LRA_MIXED_PRIO_P -1
-#endif
-#ifndef LRA_MIXED_PRIO_S
-#define LRA_MIXED_PRIO_S -1
-#endif
-#ifndef LRA_MIXED_PRIO_E
-#define LRA_MIXED_PRIO_E -1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LRA_MIXED_SETPRIO(p) do { if ((p) >= 0) __builtin_amdgcn_s_setprio((p) >= 0 ? (p) : 0); } while (0)
-#else
-#define LRA_MIXED_SETPRIO(p) ((void)0)
-#endif
+// (no wave priorities here: s_setprio per stage -- frame loads, passes, split, mel reduce -- moved nothing, profiles/r04_experiments.md 10)
 
 namespace lra {
 namespace mixed {
@@ -88,22 +71,13 @@ constexpr int stride_before(const Radices& f, int p) {
 // CU: every stage ends in a workgroup barrier and starts with loads, so what hides the latencies is OTHER workgroups in other stages.
 // Measured on the MI355X, n_fft 400 / hop 160 / 80 mels, 256 x 30 s (profiles/r04_experiments.md section 5): 16 frames per workgroup (51 KB,
 // three workgroups per CU) 1.39 ms, 12: 1.16, 8: 1.08, 6: 0.94, 4: 0.99; 64- or 128-thread workgroups 1.45-2.5 ms.
-#ifndef LRA_MIXED_NT
-#define LRA_MIXED_NT 256
-#endif
-#ifndef LRA_MIXED_FMAX
-#define LRA_MIXED_FMAX 8
-#endif
-#ifndef LRA_MIXED_LDS_KB
-#define LRA_MIXED_LDS_KB 24
-#endif
+constexpr int NT = 256;        // threads per workgroup
+constexpr int kFramesMax = 8;  // frames per workgroup at most
+constexpr int kLdsKb = 24;     // LDS budget per workgroup
 // Among the frame counts the budget allows (and down to half of that), the one whose stages waste the fewest lanes: a stage of `items` work items per
 // frame runs ceil(F items / NT) rounds of the whole workgroup, each costing about the same whether its last round is full or not -- at n_fft = 400 the
 // budget's 7 frames put 280 radix-5 butterflies into 2 rounds of 256 lanes, 6 frames put 240 into one (round 6, after the global loads stopped being what
 // the kernel waited for: the vector pipe is busy 0.76 of the time; measured 400 / 160: stft 0.518 -> 0.505 ms).  Weights ~ vector instructions per work item.
-#ifndef LRA_MIXED_FTUNE
-#define LRA_MIXED_FTUNE 1
-#endif
 constexpr int stage_rounds_cost(int M, int F, int nt) {
     const Radices f = factor(M);
     int cost = ((F * M + nt - 1) / nt) * 15 + ((F * (M / 2 + 1) + nt - 1) / nt) * 40;  // frame load, Hermitian split
@@ -115,15 +89,12 @@ constexpr int stage_rounds_cost(int M, int F, int nt) {
 }
 template <class T, int N> constexpr int frames_per_group() {
     constexpr int M = N / 2;
-    int f = (int)((LRA_MIXED_LDS_KB * 1024 - M * 2 * (int)sizeof(T)) / (2 * M * 2 * (int)sizeof(T)));
-    f = f < 1 ? 1 : (f > LRA_MIXED_FMAX ? LRA_MIXED_FMAX : f);
-    if (LRA_MIXED_FTUNE) {
-        int best = f;
-        for (int c = f - 1; c >= 1 && 2 * c >= f; --c)
-            if ((long long)stage_rounds_cost(M, c, LRA_MIXED_NT) * best < (long long)stage_rounds_cost(M, best, LRA_MIXED_NT) * c) best = c;  // cost per frame
-        f = best;
-    }
-    return f;
+    int f = (int)((kLdsKb * 1024 - M * 2 * (int)sizeof(T)) / (2 * M * 2 * (int)sizeof(T)));
+    f = f < 1 ? 1 : (f > kFramesMax ? kFramesMax : f);
+    int best = f;
+    for (int c = f - 1; c >= 1 && 2 * c >= f; --c)
+        if ((long long)stage_rounds_cost(M, c, NT) * best < (long long)stage_rounds_cost(M, best, NT) * c) best = c;  // cost per frame
+    return best;
 }
 template <class T, int N> constexpr int lds_bytes() { return (2 * frames_per_group<T, N>() * (N / 2) + N / 2) * 2 * (int)sizeof(T); }
 
@@ -131,17 +102,11 @@ template <class T, int N> constexpr int lds_bytes() { return (2 * frames_per_gro
 // per round of work items, at the very end of a workgroup's life where nothing hides them.  Up to 256 bands and 1 536 weights (one and six loads per thread,
 // issued with the frame stage's loads) go behind the W_M table for up to 9 KB; larger banks keep the cached reads.  Measured (256 x 30 s, mel): 400 / 160 / 80
 // 0.70-0.73 -> 0.615 ms, 480 / 120 / 40 1.07 -> 0.93, 800 / 200 / 80 1.05 -> 0.94, 1200 / 300 / 128 1.49 -> 1.34; a cap of 768 misses the last two, 2 560 is 1 % slower.
-#ifndef LRA_MIXED_MEL_WAVES
-#define LRA_MIXED_MEL_WAVES 6   // waves per SIMD the forward kernels are compiled for (80 VGPRs): what the LDS budget keeps resident
-#endif
-#ifndef LRA_MIXED_MEL_NNZ
-#define LRA_MIXED_MEL_NNZ 1536
-#endif
-constexpr int kMelLdsMaxBands = 256, kMelLdsMaxNnz = LRA_MIXED_MEL_NNZ;
+constexpr int kMelWaves = 6;  // waves per SIMD the forward kernels are compiled for (80 VGPRs): what the LDS budget keeps resident
+constexpr int kMelLdsMaxBands = 256, kMelLdsMaxNnz = 1536;
 template <class T> constexpr int mel_lds_bytes(int n_mels, int nnz) { return nnz * (int)sizeof(T) + 3 * n_mels * (int)sizeof(int); }
 inline bool mel_lds_fits(int n_mels, int nnz) { return n_mels >= 1 && n_mels <= kMelLdsMaxBands && nnz >= 1 && nnz <= kMelLdsMaxNnz; }
 enum { MIXED_COMPLEX = 0, MIXED_POWER = 1, MIXED_MEL = 2 };
-constexpr int NT = LRA_MIXED_NT;  // threads per workgroup
 
 template <class T> struct Args {
     const T* y;            // [batch][y_stride]
@@ -310,7 +275,7 @@ template <class T> __device__ __forceinline__ T spec_pow(cpx<T> x, int mode, T p
 }
 
 // grid = batch * groups_per_clip workgroups of NT threads; dynamic LDS = lds_bytes<T, N>()
-template <class T, int N, int MODE> __global__ __launch_bounds__(NT, (sizeof(T) == 4 && N <= 3200) ? LRA_MIXED_MEL_WAVES : 1) void mixed_stft_kernel(Args<T> a) {
+template <class T, int N, int MODE> __global__ __launch_bounds__(NT, (sizeof(T) == 4 && N <= 3200) ? kMelWaves : 1) void mixed_stft_kernel(Args<T> a) {
     constexpr int M = N / 2, F = frames_per_group<T, N>();
     LRA_MIXED_DYN_LDS(lds);
     cpx<T>* buf0 = reinterpret_cast<cpx<T>*>(lds);
@@ -324,7 +289,6 @@ template <class T, int N, int MODE> __global__ __launch_bounds__(NT, (sizeof(T) 
     // pairs and the split step's W_N^k (which depend on nothing) -- is issued before the first use: with runtime loop bounds hipcc ran the items one after
     // the other, a global round trip each (round 6: 6-10 of them per workgroup at n_fft 3200; scripts/mixed_counters.sh: waves waiting 0.71-0.75 of their
     // cycles, the vector pipe busy 0.39-0.59).
-    LRA_MIXED_SETPRIO(LRA_MIXED_PRIO_L);
     constexpr int HP = M / 2 + 1;         // pairs (k, M - k) per frame
     constexpr int IT0 = (M + NT - 1) / NT, IT1 = (F * M + NT - 1) / NT, IT3 = (F * HP + NT - 1) / NT;
     const cpx<T>* __restrict__ win2 = reinterpret_cast<const cpx<T>*>(a.win);
@@ -398,11 +362,9 @@ template <class T, int N, int MODE> __global__ __launch_bounds__(NT, (sizeof(T) 
     }
     __syncthreads();
     // (2) M-point complex FFT of every frame
-    LRA_MIXED_SETPRIO(LRA_MIXED_PRIO_P);
     cpx<T>* src = buf0;
     cpx<T>* dst = buf1;
     Passes<T, N, 0, F>::run(src, dst, twm, frames);
-    LRA_MIXED_SETPRIO(LRA_MIXED_PRIO_S);
     // (3) Hermitian split.  With E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2 and P = W_N^k O:
     //       X[k] = E - i P,   X[M-k] = conj(E) - i conj(P)      (W_N^{M-k} = -conj W_N^k),
     // so one work item per pair (k, M - k), k = 0 .. M/2, reads its two points once and writes both bins (k = 0: the DC and Nyquist bins
@@ -433,7 +395,6 @@ template <class T, int N, int MODE> __global__ __launch_bounds__(NT, (sizeof(T) 
     }
     if (MODE == MIXED_MEL) {
         __syncthreads();
-        LRA_MIXED_SETPRIO(LRA_MIXED_PRIO_E);
         // mel[m][f] = sum_i val[off_m + i] P[f][c0_m + i]: a work item per (band, frame), frames fastest -- the F frames of a band are
         // consecutive in the output
         for (int w = (int)threadIdx.x; w < a.n_mels * F; w += NT) {
@@ -500,8 +461,8 @@ template <class T> struct CqtArgs {
 };
 template <class T, int N> constexpr int cqt_frames_per_group() {
     constexpr int MP = N / 2 + 1;
-    int f = (int)((LRA_MIXED_LDS_KB * 1024 - (N / 2) * 2 * (int)sizeof(T)) / (2 * MP * 2 * (int)sizeof(T)));
-    return f < 1 ? 1 : (f > LRA_MIXED_FMAX ? LRA_MIXED_FMAX : f);
+    int f = (int)((kLdsKb * 1024 - (N / 2) * 2 * (int)sizeof(T)) / (2 * MP * 2 * (int)sizeof(T)));
+    return f < 1 ? 1 : (f > kFramesMax ? kFramesMax : f);
 }
 // (Staging the octave's CSR entries in LDS -- 12 KB for up to 1024 of them -- was measured and is slower: 62.9 against 54.7 us per octave of 64 x 30 s clips;
 // the LDS it takes costs resident workgroups, which is what hides this kernel's latencies.)
@@ -515,7 +476,7 @@ template <class T, int N> constexpr int cqt_lds_bytes() { return (2 * cqt_frames
 
 #pragma clang fp contract(off)
 template <class T> __device__ __forceinline__ cpx<T> cmadd_exact(cpx<T> acc, cpx<T> a, cpx<T> b) {  // acc + a b, as scipy.sparse's complex wrapper evaluates it
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(LRA_MIXED_NO_PK_ASM)
+#if defined(__HIP_DEVICE_COMPILE__)
     // float: the same six roundings as four packed instructions on the (re, im) register pairs -- hipcc's own packing of the lines below takes six
     // (a sum AND a difference of the two product pairs, then a move to splice their halves); this product is the octave kernel's inner loop
     if constexpr (sizeof(T) == 4) {

@@ -1,0 +1,34 @@
+#!/usr/bin/env bash
+# Device assembly of every translation unit, working tree against a parent revision: scripts/device_asm_diff.sh <rev>
+# Prints one same/DIFFERENT line per unit and exits non-zero on any difference.  Needs hipcc, no GPU.
+# Both sides are compiled with build.py's flags plus --cuda-device-only -S from the same relative layout; lines with
+# __hip_cuid_ (a hash of path and file) are dropped.  WORK=<dir> keeps the outputs and reuses the parent's; JOBS caps the jobs.
+set -euo pipefail
+rev=${1:?usage: device_asm_diff.sh <parent-revision>}
+root=$(git -C "$(dirname "$0")" rev-parse --show-toplevel)
+work=${WORK:-$(mktemp -d)}
+[ -n "${WORK:-}" ] || trap 'rm -rf "$work"' EXIT  # (a directory of our own making goes again)
+hipcc=${ROCM_PATH:-/opt/rocm}/bin/hipcc
+flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC --cuda-device-only -S -Wno-unused-command-line-argument"
+groups=$(sed -n 's/^#define LRA_INST_NUM_GROUPS \([0-9]*\).*/\1/p' "$root/librosa_amd/csrc/lra_fused.h")
+units="api mixed_inst rhythm_inst beat_inst peaks_inst chroma_inst $(seq -f inst:%g 0 $((groups - 1)))"
+
+mkdir -p "$work/parent" "$work/new"
+[ -d "$work/parent/librosa_amd" ] || git -C "$root" archive "$rev" librosa_amd/csrc include | tar -x -C "$work/parent"
+rm -rf "$work/new/librosa_amd" "$work/new/include" "$work/new"/*.s
+(cd "$root" && tar -c librosa_amd/csrc include) | tar -x -C "$work/new"
+
+for side in parent new; do
+    for u in $units; do
+        [ "$side" = parent ] && [ -s "$work/parent/$u.s" ] && continue
+        g=${u#*:}; f=${u%%:*}
+        [ "$g" = "$u" ] && def= || def=-DLRA_INST_GROUP=$g
+        echo "cd $work/$side && $hipcc $flags $def librosa_amd/csrc/lra_$f.hip -o - | grep -v __hip_cuid_ > $u.tmp && mv $u.tmp $u.s"
+    done
+done | xargs -P "${JOBS:-16}" -d '\n' -n 1 bash -o pipefail -c || true  # (a unit that does not compile leaves no .s: DIFFERENT below)
+
+rc=0
+for u in $units; do
+    if cmp -s "$work/parent/$u.s" "$work/new/$u.s"; then echo "same       $u"; else echo "DIFFERENT  $u"; rc=1; fi
+done
+exit $rc

@@ -1,4 +1,4 @@
-"""Development probe (GPU box): ablation timings and variant debugging.  Not part of the product."""
+"""Development probe (GPU box): variant timings and debugging.  Not part of the product."""
 import os
 import sys
 import time
@@ -48,17 +48,8 @@ def timeit(fn, steps=10):
     return e0.elapsed_ms(e1) / steps
 
 
-what = sys.argv[1] if len(sys.argv) > 1 else "ablate"
-if what == "ablate":
-    # run once per probe build:  LIBROSA_AMD_LIBRARY=probe/lib_abN.so python scripts/gpu_probe.py ablate
-    # (hipcc -DLRA_PROBE_ONLY -DLRA_ABLATE=N: 1 = no spectrum stores, 2 = no FFT math, stores only)
-    for variant in (0, 4):
-        ctx.set_option("variant", variant)
-        for iters in (16, 32):
-            ctx.set_option("stft_iters", iters)
-            ms = timeit(lambda: ctx.stft_exec(plan, y.data_ptr(), batch, n, n, D.data_ptr()))
-            print(f"{os.environ.get('LIBROSA_AMD_LIBRARY', 'product')}: variant {variant} iters {iters}: stft {ms:.3f} ms ({batch * T / ms / 1e3:.1f} Mframes/s)", flush=True)
-elif what == "iters":
+what = sys.argv[1] if len(sys.argv) > 1 else "iters"
+if what == "iters":
     ctx.set_option("mel_runs", int(os.environ.get("PROBE_MEL_RUNS", "1")))
     ctx.set_option("autotune", 0)
     for variant in (0, 1, 4):
@@ -99,7 +90,7 @@ elif what == "v2":
                 print(f"{os.environ.get('LIBROSA_AMD_LIBRARY', 'product')}: v2 {v2} remap {remap} iters {iters:3d}: stft {ms:.3f} ms ({batch * T * 10248 / ms / 1e6:5.0f} GB/s = {batch * T * 10248 / ms / 8e7:4.1f} %)   "
                       f"power {msp:.3f} ms ({batch * T * 6148 / msp / 1e6:5.0f} GB/s)", flush=True)
 elif what == "v2b":
-    # second-generation kernel only: XCD map x frames per slot (store-form / ablation variants are separate builds)
+    # second-generation kernel only: XCD map x frames per slot (store-form variants are separate builds)
     ctx.set_option("autotune", 0)
     ctx.set_option("variant", 0)
     ctx.set_option("v2", 1)
@@ -147,7 +138,7 @@ elif what == "survey":
               f"istft {mi:7.3f} ms ({by / mi / 1e6:6.0f} GB/s)", flush=True)
         del Dn, Mn, yr
 elif what == "occupancy":
-    # stft kernel time vs resident waves per CU (one wave64 per workgroup, 17 KB of LDS per slot + pad); run once per (ablation) build
+    # stft kernel time vs resident waves per CU (one wave64 per workgroup, 17 KB of LDS per slot + pad); run once per build
     ctx.set_option("autotune", 0)
     ctx.set_option("variant", 0)
     for waves in (9, 8, 6, 4, 3, 2, 1):

@@ -3,7 +3,7 @@
 
 Cross-compiles instantiation group 11 (lra_inst.hip) for gfx950, cuts out one stft_pc_kernel instance (default: the bench's,
 FftCfg<10,4,float,64,2,1,0,0>, hop n_fft / 4, |X|^2) and finds the consumer's frame loop(s): the depth-1 loops that hold both of the
-consumer's priorities (s_setprio LRA_PC_PRIO_CA = 0, LRA_PC_PRIO_CB = 1).  Every basic block of such a loop is counted (VALU, SALU, LDS,
+consumer's priorities (s_setprio kPcPrioCA = 0, kPcPrioCB = 1).  Every basic block of such a loop is counted (VALU, SALU, LDS,
 VMEM) and classed:
   wait   the bounded sleeping poll (s_sleep) and the sticky-flag report -- not run while the ready flag is already set
   burst  blocks that store to the output (global_store) -- a whole tile once per eight frames and band, partial tiles at slot ends

@@ -3,7 +3,7 @@
 
 Sibling of pc_consumer_isa.py (same block parser, same instruction classes).  Cross-compiles instantiation group 11 (lra_inst.hip) for
 gfx950, cuts out one stft_pc_kernel instance (default: the bench's, FftCfg<10,4,float,64,2,1,0,0>, hop n_fft / 4, |X|^2) and finds the
-producer's frame loop: the depth-1 loop that holds both of the producer's priorities (s_setprio LRA_PC_PRIO_PA = 3, LRA_PC_PRIO_PS = 2).
+producer's frame loop: the depth-1 loop that holds both of the producer's priorities (s_setprio kPcPrioPA = 3, kPcPrioPS = 2).
 Every basic block of the loop is counted (VALU, SALU, LDS, VMEM; VALU split into packed v_pk_*, other arithmetic and the rest: moves,
 selects, shifts, integer and address work) and classed:
   wait    the bounded sleeping poll on consumed[s] (s_sleep) and the sticky-flag report -- not run while the consumer keeps up

@@ -1,6 +1,6 @@
-# GPU box, one call: parity suite on the product library, the bench line, then product vs probe builds (A/B).
-#   gpurun --timeout 1500 -- 'bash scripts/run_round_checks.sh <tag> "<kinds>" <probe names...>'
-TAG=${1:-r04a}; KINDS=${2:-"stft mel"}; shift 2
+# GPU box, one call: parity suite on the product library, then the bench line.
+#   bash scripts/run_round_checks.sh <tag>
+TAG=${1:-r04a}
 OUT=${CHECKS_OUT:-checks_out}  # where the logs and the bench record go
 mkdir -p "$OUT"
 timeout 600 python -m pytest tests -m gpu -x -q > "$OUT/pytest_$TAG.log" 2>&1; tail -5 "$OUT/pytest_$TAG.log"
@@ -19,4 +19,3 @@ try:
 except Exception as e:
     print('bench parse failed', e)
 PY
-if [ $# -gt 0 ]; then timeout 600 bash scripts/ab_run.sh "$KINDS" "$@" 2>&1 | tail -40; fi
