@@ -376,6 +376,36 @@ int lra_prev_minimum_exec(lra_ctx* ctx, const void* energy, int64_t batch, int64
 int lra_chroma_exec(lra_ctx* ctx, const void* X, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
                     const void* W, int64_t n_chroma, int norm, double threshold, int has_threshold, void* out, void* work, int* nonfinite);
 
+/* ---- pitch tracking and tuning: librosa.piptrack, pitch_tuning, estimate_tuning (core/pitch.py:28-366) -----------------------------------
+ * S: magnitudes of `dtype` (device), element (b, f, t) at b * batch_stride + f * bin_stride + t * frame_stride (elements); |.| is taken on
+ * load.  bin_stride == 1 (the layout lra_spectrogram_exec writes, rows possibly padded) and frame_stride == 1 (a C-contiguous [b][f][t]
+ * array) are the two fast forms; any other strides are served by the second.  Bins bin_lo <= f < bin_hi pass the frequency mask.  A bin is
+ * a peak where x = S * (S > ref_value) has x[f] > x[f - 1] and x[f] >= x[f + 1] (bin 0 never, the last bin on the first test alone); there
+ * pitches = (f + shift) * sr / n_fft (float64, rounded once) and mags = S + 0.5 * gradient * shift with shift = -b / a of the parabola
+ * through the three bins (0 where |b| >= |a| and at the last bin); every other element is 0. */
+#define LRA_PITCH_REF_MAX 0     /* ref_value = (dtype)threshold * max over ALL bins of the frame */
+#define LRA_PITCH_REF_ROW 1     /* ref_value = ref_row[b * n_frames + t]: float64 (device), the threshold already applied */
+#define LRA_PITCH_REF_SCALAR 2  /* ref_value = ref_scalar */
+/* pitches, mags: `dtype` (device), element (b, f, t) at b * out_batch_stride + f * out_bin_stride + t * out_frame_stride; every element
+ * with f < n_bins is written. */
+int lra_piptrack_exec(lra_ctx* ctx, const void* S, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
+                      int64_t bin_lo, int64_t bin_hi, int ref_mode, double threshold, const void* ref_row, double ref_scalar, double sr, int64_t n_fft, void* pitches, void* mags,
+                      int64_t out_batch_stride, int64_t out_bin_stride, int64_t out_frame_stride);
+/* Bytes of device scratch `work` that lra_tuning_exec needs: every frame owns ceil(masked_bins / 2) peak slots (two adjacent bins are never
+ * both peaks), masked_bins = bin_hi - bin_lo. */
+int64_t lra_tuning_work_bytes(int64_t batch, int64_t n_frames, int64_t masked_bins, int dtype);
+/* estimate_tuning without the dense arrays: the tracker emits its peaks with pitch > 0, a radix select finds thr = np.median of their
+ * magnitudes (the mean of the two middle values in `dtype`; 0 without peaks), and the peaks with mag >= thr enter the histogram of
+ * lra_pitch_tuning_exec.  out: int64 [n_hist + 2] (device): the counts, the number of peaks that entered, the number of peaks.  Integer
+ * atomics only: the same bits on every run.  Nothing is read back here. */
+int lra_tuning_exec(lra_ctx* ctx, const void* S, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
+                    int64_t bin_lo, int64_t bin_hi, int ref_mode, double threshold, const void* ref_row, double ref_scalar, double sr, int64_t n_fft, const void* edges, int64_t n_hist,
+                    double bins_per_octave, void* work, void* out);
+/* pitch_tuning's histogram: of the n frequencies freq (`dtype`, device) those > 0 give residual = mod(bins_per_octave * log2(f / 27.5), 1),
+ * minus 1 where >= 0.5, in `dtype`; np.histogram(residual, edges) with edges float64 [n_hist + 1] (device), the last bin closed.
+ * out: int64 [n_hist + 2] (device): the counts, the number of frequencies > 0, 0. */
+int lra_pitch_tuning_exec(lra_ctx* ctx, const void* freq, int64_t n, int dtype, const void* edges, int64_t n_hist, double bins_per_octave, void* out);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

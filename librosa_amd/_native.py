@@ -113,6 +113,12 @@ SIGNATURES = {
     "lra_cqt_octave_supported": (c_int, [c_int]),
     "lra_cqt_octave_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int]),
     "lra_magnitude_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "lra_piptrack_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
+                                  c_void_p, c_void_p, c_int64, c_int64, c_int64]),
+    "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
+    "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
+                                c_void_p, c_int64, c_double, c_void_p, c_void_p]),
+    "lra_pitch_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_double, c_void_p]),
     "lra_chroma_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
                         POINTER(c_int)]),
     "lra_magphase_exec": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_double, c_int]),
@@ -630,6 +636,28 @@ class Context:
                                         c_void_p(w_ptr), int(n_chroma), int(norm_code), 0.0 if threshold is None else float(threshold), int(threshold is not None), c_void_p(out_ptr),
                                         c_void_p(work_ptr), byref(flag)))
         return bool(flag.value)
+
+    PITCH_REF_MAX, PITCH_REF_ROW, PITCH_REF_SCALAR = 0, 1, 2   # the LRA_PITCH_REF_* values
+
+    def piptrack_exec(self, s_ptr, batch, n_bins, n_frames, strides, dtype, bin_lo, bin_hi, ref_mode, threshold, ref_row_ptr, ref_scalar, sr, n_fft, pitches_ptr, mags_ptr, out_strides):
+        """The dense pitch tracker (``include/librosa_amd.h``: lra_piptrack_exec); ``strides`` / ``out_strides``: (batch, bin, frame) in elements."""
+        _check(self.lib.lra_piptrack_exec(self.handle, c_void_p(s_ptr), int(batch), int(n_bins), int(n_frames), int(strides[0]), int(strides[1]), int(strides[2]), dtype_code(dtype),
+                                          int(bin_lo), int(bin_hi), int(ref_mode), float(threshold), c_void_p(ref_row_ptr or None), float(ref_scalar), float(sr), int(n_fft),
+                                          c_void_p(pitches_ptr), c_void_p(mags_ptr), int(out_strides[0]), int(out_strides[1]), int(out_strides[2])))
+
+    def tuning_work_bytes(self, batch, n_frames, masked_bins, dtype):
+        return int(self.lib.lra_tuning_work_bytes(int(batch), int(n_frames), int(masked_bins), dtype_code(dtype)))
+
+    def tuning_exec(self, s_ptr, batch, n_bins, n_frames, strides, dtype, bin_lo, bin_hi, ref_mode, threshold, ref_row_ptr, ref_scalar, sr, n_fft, edges_ptr, n_hist, bins_per_octave,
+                    work_ptr, out_ptr):
+        """Peaks, their median magnitude and the tuning histogram in one native call (lra_tuning_exec); ``out``: int64 [n_hist + 2] on the device."""
+        _check(self.lib.lra_tuning_exec(self.handle, c_void_p(s_ptr), int(batch), int(n_bins), int(n_frames), int(strides[0]), int(strides[1]), int(strides[2]), dtype_code(dtype),
+                                        int(bin_lo), int(bin_hi), int(ref_mode), float(threshold), c_void_p(ref_row_ptr or None), float(ref_scalar), float(sr), int(n_fft),
+                                        c_void_p(edges_ptr), int(n_hist), float(bins_per_octave), c_void_p(work_ptr), c_void_p(out_ptr)))
+
+    def pitch_tuning_exec(self, freq_ptr, n, dtype, edges_ptr, n_hist, bins_per_octave, out_ptr):
+        """The tuning histogram of a frequency array (lra_pitch_tuning_exec); ``out``: int64 [n_hist + 2] on the device."""
+        _check(self.lib.lra_pitch_tuning_exec(self.handle, c_void_p(freq_ptr or None), int(n), dtype_code(dtype), c_void_p(edges_ptr), int(n_hist), float(bins_per_octave), c_void_p(out_ptr)))
 
     def magnitude_exec(self, d_ptr, mag_ptr, count, dtype):
         _check(self.lib.lra_magnitude_exec(self.handle, c_void_p(d_ptr), c_void_p(mag_ptr), count, dtype_code(dtype)))

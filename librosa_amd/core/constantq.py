@@ -145,7 +145,7 @@ def vqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, intervals="equal",
 
     Returns ``(..., n_bins, n_frames)`` complex (complex64 for float32 audio).  ``y`` may be a device tensor (a device tensor is
     returned; ``check_finite=False`` -- an extension, as for ``stft`` -- then skips ``valid_audio``'s finite test, whose device flag costs one
-    host synchronisation per call: back-to-back calls otherwise cannot overlap their launches with the previous call's kernels).  Not provided: ``tuning=None`` (needs the pitch tracker behind ``estimate_tuning``), named just-intonation interval
+    host synchronisation per call: back-to-back calls otherwise cannot overlap their launches with the previous call's kernels).  Not provided: ``tuning=None`` (``tuning=librosa_amd.estimate_tuning(y=y, sr=sr)`` supplies the number on the device), named just-intonation interval
     sets (``intervals`` must be ``"equal"`` or an explicit list).  See the module docstring for ``res_type``.
 
     ``_post(sess, ptr, batch, n_frames, n_bins, real) -> (handle, rows)`` (internal) chains further device work on the [batch][n_frames][n_bins]
@@ -298,7 +298,7 @@ def cqt(y, *, sr=22050, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12
         pad_mode="constant", res_type="soxr_hq", dtype=None, check_finite=True, _post=None):
     """Constant-Q transform; drop-in for ``librosa.cqt`` (``librosa/core/constantq.py:42-225``): the ``gamma=0`` case of :func:`vqt`.
     Not provided: ``tuning=None`` -- the reference estimates the tuning with its pitch tracker
-    (``core/constantq.py:318-319, 985-986`` -> ``estimate_tuning``), which is outside this library's scope: pass a number (default 0.0).
+    (``core/constantq.py:318-319, 985-986`` -> ``estimate_tuning``), which this function does not call: pass a number (default 0.0); ``tuning=librosa_amd.estimate_tuning(y=y, sr=sr)`` supplies the number on the device.
     Unpinned: the reference's DEFAULT ``res_type="soxr_hq"`` runs this library's own band-limited design (see ``resample``); ``"polyphase"`` /
     ``"fft"`` / ``"scipy"`` are pinned against the reference.
     """

@@ -41,6 +41,19 @@ def mel_to_hz(mels, *, htk=False):
     return freqs
 
 
+def hz_to_octs(frequencies, *, tuning=0.0, bins_per_octave=12):
+    """Frequencies (Hz) to fractional octave numbers relative to A0 / 2 = 27.5 Hz at ``tuning`` 0 (``librosa/core/convert.py:1146-1182``)."""
+    A440 = 440.0 * 2.0 ** (tuning / bins_per_octave)
+    octs = np.log2(np.asanyarray(frequencies) / (float(A440) / 16))
+    return octs[()]
+
+
+def octs_to_hz(octs, *, tuning=0.0, bins_per_octave=12):
+    """Octave numbers to frequencies; the inverse of ``hz_to_octs`` (``librosa/core/convert.py:1204-1241``)."""
+    A440 = 440.0 * 2.0 ** (tuning / bins_per_octave)
+    return (float(A440) / 16) * (2.0 ** np.asanyarray(octs)[()])
+
+
 def fft_frequencies(*, sr=22050, n_fft=2048):
     return np.fft.rfftfreq(n=n_fft, d=1.0 / sr)
 

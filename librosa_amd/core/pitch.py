@@ -1,0 +1,307 @@
+"""``piptrack``, ``pitch_tuning`` and ``estimate_tuning`` with librosa's signatures (``librosa/core/pitch.py:28-366``).
+
+The tracker is a three-point stencil along the bins of a magnitude spectrogram that is already on the device (``csrc/lra_pitch.h``):
+``piptrack`` writes the two dense arrays in one launch (zeros included); ``estimate_tuning`` never forms them -- the same kernel emits only
+its peaks, a radix select finds the median of their magnitudes, and the peaks at or above it enter a 1 / ``resolution``-bin integer
+histogram.  Only that counts row comes back to the host, which takes the argmax and the edge from the same ``np.linspace`` table as the
+reference.  With ``y`` given the magnitude STFT runs first and the spectrogram is never downloaded.
+
+``S`` may be a NumPy array or a device tensor, real or complex (a complex ``S`` goes through the magnitude kernel first; a real one has
+``|.|`` taken on load); a device tensor in the layout ``stft`` / ``_spectrogram`` return is read in place.  ``S`` is never written.
+
+``ref``: ``None`` / ``np.max`` and numbers are handled in the kernel.  Any other callable is the slow path: it is applied on the host to a
+NumPy copy of ``|S|`` and its per-frame row is uploaded.
+
+Documented difference: an ``S`` with fewer than two bins raises ``ParameterError`` (the reference fails incidentally there, with
+``ZeroDivisionError`` or ``np.gradient``'s ``ValueError``).  ``S`` must be floating-point or complex.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+
+from .. import _arrays
+from ..util.exceptions import ParameterError
+from ..util.utils import is_torch_tensor
+from . import convert
+from . import spectrum as _spectrum
+
+__all__ = ["piptrack", "pitch_tuning", "estimate_tuning"]
+
+_PIPTRACK_KWARGS = ("hop_length", "fmin", "fmax", "threshold", "win_length", "window", "center", "pad_mode", "ref")
+
+
+def _is_number(x):
+    return isinstance(x, (int, float, np.number)) and not isinstance(x, (bool, np.bool_))
+
+
+def _bin_range(sr, n_fft, fmin, fmax):
+    """The bins of ``freq_mask = (fmin <= fft_freqs) & (fft_freqs < fmax)`` (``core/pitch.py:326-344``, float64) as ``lo <= f < hi``."""
+    fmin = np.maximum(fmin, 0)
+    fmax = np.minimum(fmax, float(sr) / 2)
+    freqs = convert.fft_frequencies(sr=sr, n_fft=n_fft)
+    hit = np.flatnonzero((fmin <= freqs) & (freqs < fmax))
+    if hit.size == 0:
+        return 0, 0
+    lo, hi = int(hit[0]), int(hit[-1]) + 1
+    if hi - lo != hit.size:
+        raise ParameterError(f"the bins between fmin={fmin} and fmax={fmax} are not one range (sr={sr})")
+    return lo, hi
+
+
+def _check_args(sr, threshold, ref, fmin, fmax):
+    if not (_is_number(sr) and sr > 0):
+        raise ParameterError(f"sr={sr!r} must be a positive number")
+    if not _is_number(threshold):
+        raise ParameterError(f"threshold={threshold!r} must be a number")
+    if not (_is_number(fmin) and _is_number(fmax)):
+        raise ParameterError(f"fmin={fmin!r} and fmax={fmax!r} must be numbers")
+    if not (ref is None or callable(ref) or _is_number(ref)):
+        raise ParameterError(f"ref={ref!r} must be None, a number or a callable")
+
+
+def _check_S(S):
+    dtype = _arrays.numpy_dtype_of(S)
+    if dtype not in (np.float32, np.float64, np.complex64, np.complex128):
+        raise ParameterError(f"S must be floating-point or complex, given dtype={dtype}")
+    if S.ndim < 2:
+        raise ParameterError(f"S must have at least 2 dimensions, given shape={tuple(S.shape)}")
+    if S.shape[-2] < 2:
+        raise ParameterError(f"S must have at least 2 frequency bins, given shape={tuple(S.shape)}")
+    return np.dtype(np.float64) if dtype in (np.float64, np.complex128) else np.dtype(np.float32)
+
+
+def _host_ref_row(S, ref, threshold, lead, n_frames):
+    """The slow path of a callable ``ref``: ``threshold * ref(|S|, axis=-2)`` on the host, one float64 value per frame."""
+    host = S.detach().cpu().numpy() if is_torch_tensor(S) else np.asarray(S)
+    if np.iscomplexobj(host) or (host.size and host.min() < 0):
+        host = np.abs(host)
+    row = np.asarray(threshold * ref(host, axis=-2))
+    if row.ndim == host.ndim:  # (a callable that keeps the reduced axis)
+        row = np.squeeze(row, axis=-2)
+    return np.ascontiguousarray(np.broadcast_to(row, lead + (n_frames,)), dtype=np.float64)
+
+
+def _ref_args(sess, S, ref, threshold, lead, n_frames):
+    """(mode, threshold, device pointer of the per-frame row, scalar) for the kernels."""
+    ctx = sess.ctx
+    if ref is None or ref is np.max or ref is np.amax:
+        return ctx.PITCH_REF_MAX, float(threshold), 0, 0.0
+    if callable(ref):
+        row = _host_ref_row(S, ref, threshold, lead, n_frames)
+        return ctx.PITCH_REF_ROW, float(threshold), sess.input_raw(_spectrum._as_like(sess, row), np.float64), 0.0
+    return ctx.PITCH_REF_SCALAR, float(threshold), 0, float(np.abs(ref))
+
+
+def _resident(sess, S, real):
+    """Device pointer of the real magnitudes of ``S`` (..., n_bins, n_frames), its (batch, bin, frame) strides in elements, and whether that
+    is the frame-major form.  A device tensor in the layout of ``stft`` / ``_spectrogram`` is used in place; a complex ``S`` is rectified by
+    the magnitude kernel into scratch."""
+    n_bins, n_frames = int(S.shape[-2]), int(S.shape[-1])
+    dtype = _arrays.numpy_dtype_of(S)
+    St = _arrays.swap_last_two(S)  # (..., t, f)
+    if is_torch_tensor(S):
+        if dtype.kind != "c":
+            rows = _spectrum._frame_major_strides(St, n_bins)
+            if rows is not None:
+                sess._keep.append(St)
+                return St.data_ptr(), (rows[0], 1, rows[1]), True
+        frame_major = St.is_contiguous()
+    else:
+        frame_major = bool(St.flags["C_CONTIGUOUS"]) and n_frames > 1  # a view of the device layout (what our own _spectrogram returns)
+    src = St if frame_major else S
+    strides = (n_frames * n_bins, 1, n_bins) if frame_major else (n_bins * n_frames, n_frames, 1)
+    ptr = sess.input_raw(src, dtype)
+    if dtype.kind == "c":
+        count = int(np.prod(S.shape, dtype=np.int64))
+        mag = sess.scratch(count * real.itemsize)
+        sess.ctx.magnitude_exec(ptr, mag, count, real)
+        ptr = mag
+    return ptr, strides, frame_major
+
+
+def _dense(sess, s_ptr, strides, frame_major, batch, n_bins, n_frames, real, lo, hi, ref_args, sr, n_fft):
+    """One launch; returns the handle of the (2, batch, n_frames, n_bins) -- frame-major -- or (2, batch, n_bins, n_frames) result."""
+    shape = (2, batch, n_frames, n_bins) if frame_major else (2, batch, n_bins, n_frames)
+    out_ptr, handle = sess.output(shape, real)
+    out_strides = (n_frames * n_bins, 1, n_bins) if frame_major else (n_bins * n_frames, n_frames, 1)
+    mode, threshold, row_ptr, scalar = ref_args
+    sess.ctx.piptrack_exec(s_ptr, batch, n_bins, n_frames, strides, real, lo, hi, mode, threshold, row_ptr, scalar, sr, n_fft, out_ptr,
+                           out_ptr + batch * n_frames * n_bins * real.itemsize, out_strides)
+    return handle
+
+
+def _split(res, lead, n_bins, n_frames, frame_major):
+    if frame_major:
+        res = _arrays.swap_last_two(res.reshape((2,) + lead + (n_frames, n_bins)))  # the view convention of stft / _spectrogram
+    else:
+        res = res.reshape((2,) + lead + (n_bins, n_frames))
+    return res[0], res[1]
+
+
+def piptrack(*, y=None, sr=22050, S=None, n_fft=2048, hop_length=None, fmin=150.0, fmax=4000.0, threshold=0.1, win_length=None, window="hann", center=True, pad_mode="constant",
+             ref=None):
+    """Pitch tracking on the thresholded, parabolically interpolated magnitude spectrogram; drop-in for ``librosa.piptrack``
+    (``core/pitch.py:181-366``).  Returns ``(pitches, magnitudes)``, shaped and typed like ``S`` (a real array of the same precision for a
+    complex ``S``), NumPy arrays for NumPy input and device tensors for device tensors, zero everywhere but at the detected peaks.
+
+    With ``y`` the magnitude STFT and the tracker run back to back on the device.  See the module docstring for ``ref`` and the layouts."""
+    _check_args(sr, threshold, ref, fmin, fmax)
+    if S is None and y is not None and callable(ref) and not (ref is np.max or ref is np.amax):
+        S, n_fft = _spectrum._spectrogram(y=y, n_fft=n_fft, hop_length=hop_length, win_length=win_length, window=window, center=center, pad_mode=pad_mode)
+    if S is not None:
+        real = _check_S(S)
+        S, n_fft = _spectrum._spectrogram(S=S, n_fft=n_fft)
+        lead = tuple(int(s) for s in S.shape[:-2])
+        n_bins, n_frames = int(S.shape[-2]), int(S.shape[-1])
+        batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        lo, hi = _bin_range(sr, n_fft, fmin, fmax)
+        sess = _arrays.Session(S)
+        try:
+            if batch * n_frames == 0:
+                handle, frame_major = sess.output((2, batch, n_bins, n_frames), real)[1], False
+            else:
+                ref_args = _ref_args(sess, S, ref, threshold, lead, n_frames)
+                s_ptr, strides, frame_major = _resident(sess, S, real)
+                handle = _dense(sess, s_ptr, strides, frame_major, batch, n_bins, n_frames, real, lo, hi, ref_args, float(sr), n_fft)
+            res = sess.result(handle)
+        finally:
+            sess.close()
+        return _split(res, lead, n_bins, n_frames, frame_major)
+    if n_fft is None:
+        raise ParameterError(f"Unable to compute spectrogram with n_fft={n_fft}")
+    if y is None:
+        raise ParameterError("Input signal must be provided to compute a spectrogram")
+    lo, hi = _bin_range(sr, n_fft, fmin, fmax)
+    shape = {}
+
+    def post(sess, s_ptr, batch, n_bins, n_frames, pitch, real):
+        shape.update(n_bins=n_bins, n_frames=n_frames)
+        ref_args = _ref_args(sess, None, ref, threshold, (), n_frames)
+        return _dense(sess, s_ptr, (n_frames * pitch, 1, pitch), True, batch, n_bins, n_frames, real, lo, hi, ref_args, float(sr), n_fft), None
+
+    res = _spectrum._run_stft_family("power", y, n_fft=n_fft, hop_length=hop_length, win_length=win_length, window=window, center=center, pad_mode=pad_mode, power=1.0, post=post)
+    return _split(res, tuple(int(s) for s in y.shape[:-1]), shape["n_bins"], shape["n_frames"], True)
+
+
+def _edges_ptr(sess, edges):
+    ctx = sess.ctx
+    if ctx.table_cacheable(edges.nbytes):
+        return ctx.device_table(("tuning_edges", int(edges.size)), lambda: edges)
+    return sess.input_raw(_spectrum._as_like(sess, edges), np.float64)
+
+
+def _histogram_edges(resolution, bins_per_octave):
+    if not (_is_number(resolution) and resolution > 0):
+        raise ParameterError(f"resolution={resolution!r} must be a positive number")
+    if not (_is_number(bins_per_octave) and bins_per_octave > 0):
+        raise ParameterError(f"bins_per_octave={bins_per_octave!r} must be a positive number")
+    n_hist = int(np.ceil(1.0 / resolution))
+    if n_hist < 1 or n_hist > 2**31 - 3:
+        raise ParameterError(f"resolution={resolution!r} gives {n_hist} histogram bins")
+    return np.linspace(-0.5, 0.5, n_hist + 1)
+
+
+def _host_row(row):
+    return row.detach().cpu().numpy() if is_torch_tensor(row) else np.asarray(row)
+
+
+def _tuning_from_counts(row, edges, stacklevel):
+    """The histogram's first maximum and its left edge (``core/pitch.py:153-178``); ``row``: the counts, then how many frequencies entered."""
+    n_hist = edges.size - 1
+    if row is None or int(row[n_hist]) == 0:
+        warnings.warn("Trying to estimate tuning from empty frequency set.", stacklevel=stacklevel)
+        return 0.0
+    return float(edges[int(np.argmax(row[:n_hist]))])
+
+
+def _pitch_tuning_row(frequencies, resolution, bins_per_octave):
+    """``pitch_tuning`` up to the histogram: (the counts row of ``lra_pitch_tuning_exec``, or None for an empty input; the edges)."""
+    edges = _histogram_edges(resolution, bins_per_octave)
+    if not is_torch_tensor(frequencies):
+        frequencies = np.atleast_1d(frequencies)
+        if frequencies.dtype.kind not in "fiub":
+            raise ParameterError(f"frequencies must be real numbers, given dtype={frequencies.dtype}")
+        if frequencies.dtype not in (np.float32, np.float64):
+            frequencies = frequencies.astype(np.float64)
+    real = _arrays.numpy_dtype_of(frequencies)
+    if real not in (np.float32, np.float64):
+        raise ParameterError(f"frequencies must be real floating-point, given dtype={real}")
+    n = int(np.prod(frequencies.shape, dtype=np.int64))
+    if n == 0:
+        return None, edges
+    sess = _arrays.Session(frequencies)
+    try:
+        out_ptr, handle = sess.output((edges.size + 1,), np.int64)
+        sess.ctx.pitch_tuning_exec(sess.input_raw(frequencies, real), n, real, _edges_ptr(sess, edges), edges.size - 1, bins_per_octave, out_ptr)
+        row = sess.result(handle)
+    finally:
+        sess.close()
+    return _host_row(row), edges
+
+
+def pitch_tuning(frequencies, *, resolution=0.01, bins_per_octave=12):
+    """The tuning offset of a collection of frequencies relative to A440, in fractions of a bin; drop-in for ``librosa.pitch_tuning``
+    (``core/pitch.py:112-178``).  ``frequencies``: array-like or device tensor.  Returns a Python float."""
+    row, edges = _pitch_tuning_row(frequencies, resolution, bins_per_octave)
+    return _tuning_from_counts(row, edges, 3)
+
+
+def _tuning_row(y, sr, S, n_fft, resolution, bins_per_octave, kwargs):
+    """``estimate_tuning`` up to the histogram: (the counts row of ``lra_tuning_exec`` as a NumPy array, or None for an empty input; the edges)."""
+    unknown = sorted(set(kwargs) - set(_PIPTRACK_KWARGS))
+    if unknown:
+        raise TypeError(f"piptrack() got an unexpected keyword argument {unknown[0]!r}")
+    fmin, fmax, threshold, ref = kwargs.get("fmin", 150.0), kwargs.get("fmax", 4000.0), kwargs.get("threshold", 0.1), kwargs.get("ref", None)
+    stft_kwargs = {k: kwargs[k] for k in ("hop_length", "win_length", "window", "center", "pad_mode") if k in kwargs}
+    _check_args(sr, threshold, ref, fmin, fmax)
+    edges = _histogram_edges(resolution, bins_per_octave)
+    if S is None and y is not None and callable(ref) and not (ref is np.max or ref is np.amax):
+        S, n_fft = _spectrum._spectrogram(y=y, n_fft=n_fft, **{"hop_length": None, **stft_kwargs})
+
+    def run(sess, s_ptr, strides, batch, n_bins, n_frames, real, lo, hi, ref_args):
+        out_ptr, handle = sess.output((edges.size + 1,), np.int64)
+        mode, thr, row_ptr, scalar = ref_args
+        work = sess.scratch(sess.ctx.tuning_work_bytes(batch, n_frames, hi - lo, real))
+        sess.ctx.tuning_exec(s_ptr, batch, n_bins, n_frames, strides, real, lo, hi, mode, thr, row_ptr, scalar, float(sr), n_fft, _edges_ptr(sess, edges), edges.size - 1,
+                             bins_per_octave, work, out_ptr)
+        return handle
+
+    if S is not None:
+        real = _check_S(S)
+        S, n_fft = _spectrum._spectrogram(S=S, n_fft=n_fft)
+        lead = tuple(int(s) for s in S.shape[:-2])
+        n_bins, n_frames = int(S.shape[-2]), int(S.shape[-1])
+        batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        lo, hi = _bin_range(sr, n_fft, fmin, fmax)
+        if batch * n_frames == 0:
+            return None, edges
+        sess = _arrays.Session(S)
+        try:
+            ref_args = _ref_args(sess, S, ref, threshold, lead, n_frames)
+            s_ptr, strides, _ = _resident(sess, S, real)
+            row = sess.result(run(sess, s_ptr, strides, batch, n_bins, n_frames, real, lo, hi, ref_args))
+        finally:
+            sess.close()
+        return _host_row(row), edges
+    if n_fft is None:
+        raise ParameterError(f"Unable to compute spectrogram with n_fft={n_fft}")
+    if y is None:
+        raise ParameterError("Input signal must be provided to compute a spectrogram")
+    lo, hi = _bin_range(sr, n_fft, fmin, fmax)
+
+    def post(sess, s_ptr, batch, n_bins, n_frames, pitch, real):
+        ref_args = _ref_args(sess, None, ref, threshold, (), n_frames)
+        return run(sess, s_ptr, (n_frames * pitch, 1, pitch), batch, n_bins, n_frames, real, lo, hi, ref_args), None
+
+    row = _spectrum._run_stft_family("power", y, n_fft=n_fft, power=1.0, post=post, **{"hop_length": None, "win_length": None, "window": "hann", "center": True, "pad_mode": "constant", **stft_kwargs})
+    return _host_row(row), edges
+
+
+def estimate_tuning(*, y=None, sr=22050, S=None, n_fft=2048, resolution=0.01, bins_per_octave=12, **kwargs):
+    """The tuning of a signal or a spectrogram; drop-in for ``librosa.estimate_tuning`` (``core/pitch.py:28-109``).  ``kwargs`` go to
+    ``piptrack``.  All leading dimensions count towards one estimate.  Returns a Python float; the dense ``piptrack`` arrays are never formed
+    and only the histogram's counts leave the device, so ``chroma_stft(y=y, sr=sr, tuning=estimate_tuning(y=y, sr=sr))`` stays resident."""
+    row, edges = _tuning_row(y, sr, S, n_fft, resolution, bins_per_octave, kwargs)
+    return _tuning_from_counts(row, edges, 3)

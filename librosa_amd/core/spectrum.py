@@ -407,7 +407,8 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
 
     With ``kind="power"`` the hook is ``post(sess, s_ptr, batch, n_bins, n_frames, pitch, real) -> (handle, rows)``: ``s_ptr`` is the power
     spectrogram [batch][n_frames][pitch] on the device (``pitch >= n_bins`` elements between the rows of consecutive frames); the spectrogram is
-    not downloaded and the result is the ``(..., rows, n_frames)`` array of ``handle`` (``feature.chroma_stft``)."""
+    not downloaded and the result is the ``(..., rows, n_frames)`` array of ``handle`` (``feature.chroma_stft``), or, with ``rows`` None, the
+    array of ``handle`` as the hook shaped it (``piptrack``, ``estimate_tuning``)."""
     need_device_check = _validate_audio(y, check_finite)
     y, hop, fft_window, center, pad_mode = _prepare_stft(y, n_fft, hop_length, win_length, window, center, pad_mode)
     in_dtype = _arrays.numpy_dtype_of(y)
@@ -549,7 +550,7 @@ def _run_stft_family(kind, y, *, n_fft, hop_length, win_length, window, center, 
     if kind == "mel":
         return res.reshape(lead + (n_mels, n_frames))
     if kind == "power" and post is not None:
-        return res.reshape(lead + (int(post_rows), n_frames))
+        return res if post_rows is None else res.reshape(lead + (int(post_rows), n_frames))
     if pitch != n_bins:
         res = res.view(lead + (n_frames, pitch))[..., :n_bins]  # the padding stays behind the view
     res = _arrays.swap_last_two(res.reshape(lead + (n_frames, n_bins)))  # (..., n_bins, n_frames) view

@@ -10,7 +10,7 @@ unnormalised result through the host ``util.normalize``.  A non-finite value rai
 ``None`` included, as the reference's ``normalize`` does.
 
 Not provided: ``tuning=None`` (the reference's default: it estimates the tuning with its pitch tracker, ``estimate_tuning`` / ``piptrack``,
-which is outside this library's scope) -- pass a number; ``chroma_cqt(cqt_mode="hybrid")``; complex ``S`` / ``C``.
+which these functions do not call) -- pass a number: ``tuning=librosa_amd.estimate_tuning(y=y, sr=sr)`` supplies the number on the device; ``chroma_cqt(cqt_mode="hybrid")``; complex ``S`` / ``C``.
 """
 from __future__ import annotations
 
@@ -131,7 +131,7 @@ def chroma_stft(*, y=None, sr=22050, S=None, norm=np.inf, n_fft=2048, hop_length
     returns for device tensors is read in place.  The result has the dtype of ``S`` / ``y`` (float64 when the bank is: ``dtype=np.float64``).
 
     Not provided: ``tuning=None`` -- the reference's default, which estimates the tuning from the spectrogram with its pitch tracker
-    (``estimate_tuning``).  Pass a number (``0.0``: A440).  ``check_finite`` (an extension, as for ``stft``) controls the scan of a device ``y``.
+    (``estimate_tuning``).  Pass a number (``0.0``: A440); ``tuning=librosa_amd.estimate_tuning(y=y, sr=sr)`` supplies the number on the device.  ``check_finite`` (an extension, as for ``stft``) controls the scan of a device ``y``.
     """
     if tuning is None:
         raise ParameterError(_NO_TUNING)
@@ -173,7 +173,8 @@ def chroma_cqt(*, y=None, sr=22050, C=None, hop_length=512, fmin=None, norm=np.i
     downloaded.  With ``C`` (constant-Q magnitudes, NumPy array or device tensor) only the chroma kernel runs.  ``threshold``: raw chroma
     values below it are set to zero before the normalisation (``None``: no threshold).  ``window`` goes to ``filters.cq_to_chroma``.
 
-    Not provided: ``tuning=None`` with ``y`` -- the reference's default, which estimates the tuning with its pitch tracker; pass a number
+    Not provided: ``tuning=None`` with ``y`` -- the reference's default, which estimates the tuning with its pitch tracker; pass a number --
+    ``tuning=librosa_amd.estimate_tuning(y=y, sr=sr)`` supplies the number on the device --
     (``C`` given, ``tuning`` is not used, as in the reference) -- and ``cqt_mode="hybrid"``.
     """
     if bins_per_octave is None:
