@@ -3369,6 +3369,8 @@ int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch,
     if (!x || !out || !taps) return fail(LRA_EINVAL, "null data pointer");
     if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "fir_decimate: dtype must be LRA_F32 or LRA_F64");
     const size_t elem = dtype == LRA_F64 ? 8 : 4;
+    // The selection below exists in three copies that have to stay in step: here, fir_route() of tests/hostsim/postsim.cpp (what the host simulator
+    // runs) and route() of tests/resample_cases.py (what the device tests expect each case to exercise; tests/test_resample_host.py compares the two).
     // four outputs per thread (four independent chains, a quarter of the workgroups) where the longer span still fits 32 KB of LDS and the job is big
     const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
     const int opt = four ? 4 : 1;

@@ -160,21 +160,32 @@ int postsim_resample_poly(const void* x, void* out, long long batch, long long n
     return 0;
 }
 
+// The kernel lra_fir_decimate_exec (lra_api.hip) selects, repeated by hand: four outputs per thread for big jobs whose span fits (the halving form where down == 2
+// and its padded span of pairs fits too), else one; the direct kernel for spans beyond the LDS.  tests/resample_cases.py::route() is the third copy;
+// tests/test_resample_host.py holds this one to it.
+enum FirRoute { kFirHalve4 = 0, kFirOpt4 = 1, kFirOpt1 = 2, kFirDirect = 3 };
+static FirRoute fir_route(long long n_out, int n_taps, int down, size_t elem) {
+    const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
+    const size_t span2 = (size_t)1023 * 2 + n_taps;
+    if (four && down == 2 && (span2 + span2 / 8 + 1) * 2 * elem <= 64 * 1024) return kFirHalve4;
+    if (four) return kFirOpt4;
+    return ((size_t)(255 * (long long)down + n_taps)) * elem > 64 * 1024 ? kFirDirect : kFirOpt1;
+}
+int postsim_fir_route(long long n_out, int n_taps, int down, int is_f64) { return (int)fir_route(n_out, n_taps, down, is_f64 ? 8 : 4); }
+
 // the launches of lra_fir_decimate_exec / lra_cqt_project_exec (lra_api.hip)
 int postsim_fir_decimate(const void* x, void* out, long long batch, long long n_in, long long n_out, const void* taps, int n_taps, int down, int first, double div, double mul, int is_f64) {
-    // (as lra_fir_decimate_exec, lra_api.hip: four outputs per thread for big jobs whose span fits, else one; the direct kernel for spans beyond the LDS)
-    const size_t elem = is_f64 ? 8 : 4;
-    const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
+    const FirRoute route = fir_route(n_out, n_taps, down, is_f64 ? 8 : 4);
+    const bool four = route == kFirHalve4 || route == kFirOpt4;
     const int opt = four ? 4 : 1;
     const int blocks_per_clip = (int)((n_out + 256 * opt - 1) / (256 * opt));
-    const size_t span2 = (size_t)1023 * 2 + n_taps;
-    if (four && down == 2 && (span2 + span2 / 8 + 1) * 2 * elem <= 64 * 1024) {
+    if (route == kFirHalve4) {
         const unsigned grid2 = (unsigned)(blocks_per_clip * batch);
         if (is_f64) run_grid(grid2, 256, [=] { lra::fir_halve4_kernel<double>((const double*)x, (double*)out, (const double*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
         else run_grid(grid2, 256, [=] { lra::fir_halve4_kernel<float>((const float*)x, (float*)out, (const float*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
         return 0;
     }
-    if ((size_t)((256 * opt - 1) * down + n_taps) * elem > 64 * 1024) {
+    if (route == kFirDirect) {
         const unsigned dgrid = (unsigned)((batch * n_out + 255) / 256);
         if (is_f64)
             run_grid_serial(dgrid, 256, [=] { lra::fir_decimate_direct_kernel<double>((const double*)x, (double*)out, (const double*)taps, batch, n_in, n_out, n_taps, down, first, div, mul); });

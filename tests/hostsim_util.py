@@ -166,6 +166,7 @@ def post_lib():
         _post.postsim_maxfilter.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_int, c.c_longlong, c.c_int, c.c_int]
         _post.postsim_fir_decimate.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_longlong, c.c_longlong, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_int]
         _post.postsim_resample_poly.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_longlong, c.c_longlong, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_int]
+        _post.postsim_fir_route.argtypes = [c.c_longlong, c.c_int, c.c_int, c.c_int]
         _post.postsim_magnitude.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_int]
         _post.postsim_magphase.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_longlong, c.c_double, c.c_int]
         _post.postsim_hpss.argtypes = [c.c_void_p] * 4 + [c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_double, c.c_int, c.c_int]
@@ -229,6 +230,11 @@ def fir_decimate(x, taps, down, first, n_out, div=1.0, mul=1.0):
     out = np.full((x.shape[0], n_out), np.nan, dtype=x.dtype)
     post_lib().postsim_fir_decimate(_p(x), _p(out), x.shape[0], x.shape[1], n_out, _p(taps), len(taps), int(down), int(first), float(div), float(mul), int(x.dtype == np.float64))
     return out
+
+
+def fir_route(n_out, n_taps, down, is_f64):
+    """The kernel the simulator's fir_decimate runs for these sizes: "halve4" | "opt4" | "opt1" | "direct" (postsim.cpp's copy of lra_fir_decimate_exec's selection)."""
+    return ("halve4", "opt4", "opt1", "direct")[post_lib().postsim_fir_route(int(n_out), int(n_taps), int(down), int(bool(is_f64)))]
 
 
 def resample_poly(x, taps, up, down, first, n_out, div=1.0, mul=1.0):

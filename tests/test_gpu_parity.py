@@ -1888,7 +1888,8 @@ def test_pcen_full_size_properties(L):
 # ---- constant-Q / variable-Q transform (librosa/core/constantq.py:42-225, 820-1122) -----------------------------
 # float32: the octave STFTs carry the forward kernel's own error (~2e-7 of their peak), the projection sums up to a few hundred of
 # their bins: 2e-5 of the transform's peak.  float64: 1e-11.  Between octaves the decimated signals are bit-identical to scipy's
-# resample_poly (tests/test_hostsim.py), so nothing accumulates down the recursion.
+# resample_poly (tests/test_hostsim.py; on the device: tests/test_resample_gpu.py, every kernel of the decimator and the halving chain), so nothing accumulates
+# down the recursion.
 def _cqt_close(C, ref):
     tol = 1e-11 if C.dtype == np.complex128 else 2e-5
     return C.shape == ref.shape and C.dtype == ref.dtype and np.abs(C - ref).max() <= tol * np.abs(ref).max()
