@@ -406,6 +406,25 @@ int lra_tuning_exec(lra_ctx* ctx, const void* S, int64_t batch, int64_t n_bins, 
  * out: int64 [n_hist + 2] (device): the counts, the number of frequencies > 0, 0. */
 int lra_pitch_tuning_exec(lra_ctx* ctx, const void* freq, int64_t n, int dtype, const void* edges, int64_t n_hist, double bins_per_octave, void* out);
 
+/* ---- yin and the front half of pyin: librosa.yin, librosa/core/pitch.py:369-628 ------------------------------------------------------- */
+#define LRA_YIN_F0 0      /* f0: float64 [batch][n_frames]; nothing dense is written */
+#define LRA_YIN_FRAMES 1  /* frames, shifts: `dtype` [batch][max_period - min_period + 1][n_frames]: the CMND and the parabolic shifts */
+/* y: [batch][n] samples of `dtype` (device), never written.  center != 0: np.pad(y, frame_length // 2, mode=pad_mode) folded into the load
+ * (pad_mode: 0 constant, 1 reflect, 2 edge, 3 symmetric); n_frames = 1 + (n + 2 pad - frame_length) / hop_length.  Per frame, in float64:
+ * d(k) = 2 (acf(0) - acf(k)) - E(k - 1) for k = 1 .. max_period with E = cumsum(y^2) and E(0) read as 0 (:394-406), the cumulative mean
+ * normalised difference c = d(k) / (mean(d(1 .. k)) + tiny) for min_period <= k <= max_period (:408-418) and the parabolic shifts
+ * (:421-477).  F0: the first trough of c below trough_threshold (util.localmin, with c[0] < c[1] at the first lag), else np.argmin(c);
+ * f0 = sr / (min_period + index + shift) (:595-628).  1 <= min_period < max_period <= frame_length - 1.  The autocorrelation goes through the
+ * smallest mixed-radix transform of at least frame_length + max_period points, or a direct sum where there is none.  The direct sum keeps
+ * 16 max_period bytes in LDS: lra_yin_lds_bytes above LRA_YIN_LDS_MAX is refused (LRA_EINVAL).  Pointers of the other mode may be NULL. */
+/* Bytes of LDS a workgroup of lra_yin_exec needs for these sizes (host arithmetic only, no device is touched); the call is served when this
+ * is at most LRA_YIN_LDS_MAX.  Only a direct-kernel call (frame_length + max_period above the largest compiled transform, 4800) with
+ * max_period > 10239 exceeds it. */
+#define LRA_YIN_LDS_MAX (160 * 1024)
+int64_t lra_yin_lds_bytes(int frame_length, int max_period);
+int lra_yin_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, int dtype, int frame_length, int hop_length, int center, int pad_mode, int min_period, int max_period,
+                 double trough_threshold, double sr, int mode, void* f0, void* frames, void* shifts);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

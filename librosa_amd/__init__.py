@@ -18,11 +18,11 @@ calls raise ``librosa_amd.NativeError``.
 """
 from . import beat, core, decompose, effects, feature, filters, onset, util
 from ._native import NativeError, device_count, get_context
-from .core import (_spectrogram, amplitude_to_db, estimate_tuning, piptrack, pitch_tuning, hz_to_octs, octs_to_hz, cqt, interval_frequencies, vqt, db_to_amplitude, db_to_power, fft_frequencies, fourier_tempo_frequencies, griffinlim, hz_to_mel, istft, magphase, pcen, phase_vocoder, mel_frequencies, mel_to_hz,
+from .core import (_spectrogram, amplitude_to_db, estimate_tuning, piptrack, pitch_tuning, yin, hz_to_octs, octs_to_hz, cqt, interval_frequencies, vqt, db_to_amplitude, db_to_power, fft_frequencies, fourier_tempo_frequencies, griffinlim, hz_to_mel, istft, magphase, pcen, phase_vocoder, mel_frequencies, mel_to_hz,
                    power_to_db, resample, stft, stream, tempo_frequencies, frames_to_samples, frames_to_time, samples_to_frames, samples_to_time, time_to_frames, time_to_samples)
 from .util.exceptions import LibrosaError, ParameterError
 
 __version__ = "0.1.0"
 
-__all__ = ["beat", "core", "decompose", "effects", "feature", "filters", "onset", "util", "stft", "istft", "_spectrogram", "magphase", "griffinlim", "phase_vocoder", "pcen", "cqt", "vqt", "interval_frequencies", "stream", "resample", "power_to_db", "amplitude_to_db", "db_to_power", "db_to_amplitude", "hz_to_mel", "mel_to_hz", "fft_frequencies", "tempo_frequencies", "fourier_tempo_frequencies", "mel_frequencies", "frames_to_samples", "samples_to_frames", "frames_to_time", "time_to_frames", "samples_to_time", "time_to_samples", "piptrack", "pitch_tuning", "estimate_tuning", "hz_to_octs", "octs_to_hz",
+__all__ = ["beat", "core", "decompose", "effects", "feature", "filters", "onset", "util", "stft", "istft", "_spectrogram", "magphase", "griffinlim", "phase_vocoder", "pcen", "cqt", "vqt", "interval_frequencies", "stream", "resample", "power_to_db", "amplitude_to_db", "db_to_power", "db_to_amplitude", "hz_to_mel", "mel_to_hz", "fft_frequencies", "tempo_frequencies", "fourier_tempo_frequencies", "mel_frequencies", "frames_to_samples", "samples_to_frames", "frames_to_time", "time_to_frames", "samples_to_time", "time_to_samples", "piptrack", "pitch_tuning", "estimate_tuning", "yin", "hz_to_octs", "octs_to_hz",
            "LibrosaError", "ParameterError", "NativeError", "device_count", "get_context"]

@@ -115,6 +115,8 @@ SIGNATURES = {
     "lra_magnitude_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int]),
     "lra_piptrack_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                   c_void_p, c_void_p, c_int64, c_int64, c_int64]),
+    "lra_yin_lds_bytes": (c_int64, [c_int, c_int]),
+    "lra_yin_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -636,6 +638,14 @@ class Context:
                                         c_void_p(w_ptr), int(n_chroma), int(norm_code), 0.0 if threshold is None else float(threshold), int(threshold is not None), c_void_p(out_ptr),
                                         c_void_p(work_ptr), byref(flag)))
         return bool(flag.value)
+
+    YIN_F0, YIN_FRAMES = 0, 1   # the LRA_YIN_* values
+
+    def yin_exec(self, y_ptr, batch, n, dtype, frame_length, hop_length, center, pad_mode, min_period, max_period, trough_threshold, sr, mode, f0_ptr=0, frames_ptr=0, shifts_ptr=0):
+        """YIN's f0 per frame, or the CMND and the parabolic shifts of every lag (``include/librosa_amd.h``: lra_yin_exec); ``pad_mode``: np.pad's name."""
+        _check(self.lib.lra_yin_exec(self.handle, c_void_p(y_ptr), int(batch), int(n), dtype_code(dtype), int(frame_length), int(hop_length), int(bool(center)),
+                                     {"constant": 0, "reflect": 1, "edge": 2, "symmetric": 3}[pad_mode], int(min_period), int(max_period), float(trough_threshold), float(sr), int(mode),
+                                     c_void_p(f0_ptr or None), c_void_p(frames_ptr or None), c_void_p(shifts_ptr or None)))
 
     PITCH_REF_MAX, PITCH_REF_ROW, PITCH_REF_SCALAR = 0, 1, 2   # the LRA_PITCH_REF_* values
 

@@ -5,7 +5,7 @@ one core, so the instances are split into groups (``csrc/lra_fused.h``) that are
 ``lra_inst.hip`` once per group plus ``lra_api.hip`` (host API, general rocFFT path), ``lra_mixed_inst.hip`` and
 ``lra_rhythm_inst.hip`` (the tempogram kernels), ``lra_beat_inst.hip`` (the beat tracker), ``lra_peaks_inst.hip``
 (the peak picker), ``lra_chroma_inst.hip`` (the chroma kernels) and ``lra_pitch_inst.hip`` (the pitch tracker and the tuning
-estimate), then one link.  The
+estimate) and ``lra_yin_inst.hip`` (YIN), then one link.  The
 result ``librosa_amd/_liblibrosa_amd.so`` is git-ignored but travels to the GPU box with the repo snapshot.
 hipcc cross-compiles for gfx950 without a GPU.
 """
@@ -66,6 +66,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT):
     jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_peaks_inst.hip"), "-o", os.path.join(OBJ, f"peaks{tag}.o")])
     jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_chroma_inst.hip"), "-o", os.path.join(OBJ, f"chroma{tag}.o")])
     jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_pitch_inst.hip"), "-o", os.path.join(OBJ, f"pitch{tag}.o")])
+    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_yin_inst.hip"), "-o", os.path.join(OBJ, f"yin{tag}.o")])
     for g in range(n_groups()):
         jobs.append([hipcc, *FLAGS, *extra_flags, f"-DLRA_INST_GROUP={g}", "-c", os.path.join(CSRC, "lra_inst.hip"), "-o", os.path.join(OBJ, f"inst{tag}_{g}.o")])
 

@@ -1,4 +1,4 @@
-"""``piptrack``, ``pitch_tuning`` and ``estimate_tuning`` with librosa's signatures (``librosa/core/pitch.py:28-366``).
+"""``piptrack``, ``pitch_tuning``, ``estimate_tuning`` and ``yin`` with librosa's signatures (``librosa/core/pitch.py:28-628``).
 
 The tracker is a three-point stencil along the bins of a magnitude spectrogram that is already on the device (``csrc/lra_pitch.h``):
 ``piptrack`` writes the two dense arrays in one launch (zeros included); ``estimate_tuning`` never forms them -- the same kernel emits only
@@ -12,6 +12,15 @@ reference.  With ``y`` given the magnitude STFT runs first and the spectrogram i
 ``ref``: ``None`` / ``np.max`` and numbers are handled in the kernel.  Any other callable is the slow path: it is applied on the host to a
 NumPy copy of ``|S|`` and its per-frame row is uploaded.
 
+``yin`` is one launch of ``csrc/lra_yin.h`` that reads the samples once and writes one float64 per frame: the autocorrelation of every frame
+through a mixed-radix transform (a direct sum where no compiled size holds ``frame_length + max_period``), the difference function, its
+cumulative mean normalisation, the first trough below the threshold and the parabola at that lag.  Everything after the load is float64, for
+float32 samples too, and ``f0`` is float64 as the reference's is.  ``_yin_frames`` returns the dense front half that ``pyin`` shares.
+
+Documented difference: ``yin`` with ``frame_length + max_period > 4800`` (no compiled transform) and ``max_period > 10239`` raises
+``ParameterError`` before any device work: the direct kernel keeps 16 bytes per lag in a workgroup's 160 KiB of LDS (sr 44100,
+``frame_length=16384``, ``fmin=4`` is such a call; the reference accepts it).
+
 Documented difference: an ``S`` with fewer than two bins raises ``ParameterError`` (the reference fails incidentally there, with
 ``ZeroDivisionError`` or ``np.gradient``'s ``ValueError``).  ``S`` must be floating-point or complex.
 """
@@ -21,14 +30,16 @@ import warnings
 
 import numpy as np
 
-from .. import _arrays
+from .. import _arrays, _native
 from ..util.exceptions import ParameterError
-from ..util.utils import is_torch_tensor
+from ..util.utils import is_torch_tensor, valid_audio
 from . import convert
 from . import spectrum as _spectrum
 
-__all__ = ["piptrack", "pitch_tuning", "estimate_tuning"]
+__all__ = ["piptrack", "pitch_tuning", "estimate_tuning", "yin"]
 
+_YIN_F0, _YIN_FRAMES = 0, 1  # the LRA_YIN_* values
+_YIN_LDS_MAX = 160 * 1024  # LRA_YIN_LDS_MAX
 _PIPTRACK_KWARGS = ("hop_length", "fmin", "fmax", "threshold", "win_length", "window", "center", "pad_mode", "ref")
 
 
@@ -305,3 +316,105 @@ def estimate_tuning(*, y=None, sr=22050, S=None, n_fft=2048, resolution=0.01, bi
     and only the histogram's counts leave the device, so ``chroma_stft(y=y, sr=sr, tuning=estimate_tuning(y=y, sr=sr))`` stays resident."""
     row, edges = _tuning_row(y, sr, S, n_fft, resolution, bins_per_octave, kwargs)
     return _tuning_from_counts(row, edges, 3)
+
+
+def _check_yin_params(*, sr, fmax, fmin, frame_length):
+    """``__check_yin_params`` (``core/pitch.py:934-968``), with its messages."""
+    if fmax > sr / 2:
+        raise ParameterError(f"fmax={fmax:.3f} cannot exceed Nyquist frequency {sr/2}")
+    if fmin >= fmax:
+        raise ParameterError(f"fmin={fmin:.3f} must be less than fmax={fmax:.3f}")
+    if fmin <= 0:
+        raise ParameterError(f"fmin={fmin:.3f} must be strictly positive")
+    if sr / fmin >= frame_length - 1:
+        fmin_feasible = sr / (frame_length - 1)
+        frame_length_feasible = int(np.ceil(sr / fmin) + 1)
+        raise ParameterError(f"fmin={fmin:.3f} is too small for frame_length={frame_length} and sr={sr}. "
+                             f"Either increase to fmin={fmin_feasible:.3f} or frame_length={frame_length_feasible}")
+    if sr / fmin >= frame_length // 2:
+        fmin_optimal = sr / (frame_length / 2)
+        frame_length_optimal = int(np.ceil(sr / fmin) * 2 + 1)
+        warnings.warn(f"With fmin={fmin:.3f}, sr={sr} and frame_length={frame_length}, less than two periods of fmin "
+                      f"fit into the frame, which can cause inaccurate pitch detection. "
+                      f"Consider increasing to fmin={fmin_optimal:.3f} or frame_length={frame_length_optimal}.", stacklevel=5)
+
+
+def _yin_prepare(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode):
+    """Every check of the reference's ``yin`` in its order (``core/pitch.py:562-585``), before any device work.  Returns the samples (padded
+    on the host for a pad mode the kernel does not fold into its load), their real type, hop, centre flag, pad mode and both periods."""
+    if fmin is None or fmax is None:
+        raise ParameterError('both "fmin" and "fmax" must be provided')
+    _check_yin_params(sr=sr, fmax=fmax, fmin=fmin, frame_length=frame_length)
+    if hop_length is None:
+        hop_length = frame_length // 4
+    if is_torch_tensor(y):
+        _spectrum._validate_audio(y, True)
+        if not _spectrum._all_finite(y):
+            raise ParameterError("Audio buffer is not finite everywhere")
+    else:
+        valid_audio(y)
+    real = np.dtype(np.float64) if _arrays.numpy_dtype_of(y) == np.float64 else np.dtype(np.float32)
+    center = bool(center)
+    if center and not (isinstance(pad_mode, str) and pad_mode in _spectrum._DEVICE_PAD_MODES):
+        if is_torch_tensor(y):
+            raise ParameterError(f"pad_mode={pad_mode!r} is only supported for numpy inputs")
+        widths = [(0, 0)] * y.ndim
+        widths[-1] = (frame_length // 2, frame_length // 2)
+        y = np.pad(y, widths, mode=pad_mode)
+        center = False
+    if not center:
+        pad_mode = "constant"
+    n = int(y.shape[-1]) + (2 * (frame_length // 2) if center else 0)
+    if n < frame_length:
+        raise ParameterError(f"Input is too short (n={n:d}) for frame_length={frame_length:d}")
+    if hop_length < 1:
+        raise ParameterError(f"Invalid hop_length: {hop_length:d}")
+    min_period = int(np.floor(sr / fmax))
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - 1)
+    if _native.load_library().lra_yin_lds_bytes(int(frame_length), max_period) > _YIN_LDS_MAX:
+        # documented difference: no compiled transform holds frame_length + max_period and the direct kernel's two rows of lags outgrow a workgroup's LDS
+        raise ParameterError(f"fmin={fmin:.3f} gives max_period={max_period}, too long for frame_length={frame_length} on the device: "
+                             f"the direct kernel serves max_period <= {_YIN_LDS_MAX // 16 - 1}")
+    return y, real, int(hop_length), center, pad_mode, min_period, max_period
+
+
+def _yin_run(y, mode, fmin, fmax, sr, frame_length, hop_length, trough_threshold, center, pad_mode):
+    y, real, hop, center, pad_mode, min_period, max_period = _yin_prepare(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode)
+    lead = tuple(int(s) for s in y.shape[:-1])
+    n = int(y.shape[-1])
+    batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    n_frames = 1 + (n + (2 * (frame_length // 2) if center else 0) - frame_length) // hop
+    n_lags = max_period - min_period + 1
+    sess = _arrays.Session(y)
+    try:
+        ctx = sess.ctx
+        frames = mode == _YIN_FRAMES
+        out_ptr, handle = sess.output((2, batch, n_lags, n_frames) if frames else (batch, n_frames), real if frames else np.float64)
+        if batch > 0:
+            y_ptr = sess.input_2d(y, real)[0]
+            half = batch * n_lags * n_frames * real.itemsize
+            ctx.yin_exec(y_ptr, batch, n, real, frame_length, hop, center, pad_mode, min_period, max_period, float(trough_threshold), float(sr), mode,
+                         f0_ptr=0 if frames else out_ptr, frames_ptr=out_ptr if frames else 0, shifts_ptr=out_ptr + half if frames else 0)
+        res = sess.result(handle)
+    finally:
+        sess.close()
+    if frames:
+        res = res.reshape((2,) + lead + (n_lags, n_frames))
+        return res[0], res[1], min_period
+    return res.reshape(lead + (n_frames,))
+
+
+def yin(y, *, fmin, fmax, sr=22050, frame_length=2048, hop_length=None, trough_threshold=0.1, center=True, pad_mode="constant"):
+    """Fundamental frequency estimation with the YIN algorithm; drop-in for ``librosa.yin`` (``core/pitch.py:480-628``).
+
+    ``y``: (..., n) NumPy array or device tensor, float32 or float64.  Returns ``f0`` (..., n_frames) in float64: a NumPy array for NumPy input,
+    a device tensor for a device tensor.  ``pad_mode``: "constant", "reflect", "edge" and "symmetric" are folded into the kernel's load; any
+    other ``np.pad`` mode is applied on the host, for NumPy input only.  ``y`` is never written."""
+    return _yin_run(y, _YIN_F0, fmin, fmax, sr, frame_length, hop_length, trough_threshold, center, pad_mode)
+
+
+def _yin_frames(y, *, fmin, fmax, sr=22050, frame_length=2048, hop_length=None, center=True, pad_mode="constant"):
+    """The front half ``yin`` and ``pyin`` share (``core/pitch.py:583-593``): ``(yin_frames, parabolic_shifts, min_period)`` with the cumulative
+    mean normalised difference function and the parabolic shifts as (..., max_period - min_period + 1, n_frames) arrays of ``y``'s type
+    (computed in float64 and rounded once)."""
+    return _yin_run(y, _YIN_FRAMES, fmin, fmax, sr, frame_length, hop_length, 0.0, center, pad_mode)

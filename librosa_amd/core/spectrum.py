@@ -712,7 +712,10 @@ def istft(stft_matrix, *, hop_length=None, win_length=None, n_fft=None, window="
                         lo, hi = max(first, 0), min(first + m, int(expected))
                         w_sh[lo - first : hi - first] = wss[lo:hi]
                         part = np.empty((batch, m), dtype=real)
-                        c.istft_exec_host(pl, Dt.ctypes.data + fa * n_bins * cplx.itemsize, batch, n_total, fb - fa, w_sh.ctypes.data, part.ctypes.data, m, m)
+                        for b in range(batch):
+                            # one item at a time, its run of frames only: an item of n_total frames taken from frame fa on would end fa frames past the spectrogram
+                            c.istft_exec_host(pl, Dt.ctypes.data + (b * n_total + fa) * n_bins * cplx.itemsize, 1, fb - fa, fb - fa, w_sh.ctypes.data,
+                                              part.ctypes.data + b * m * real.itemsize, m, m)
                         reach = min(s1, first + m)  # (`length` beyond the last frame's end: zeros there, core/spectrum.py:553-555)
                         yh[:, s0:reach] = part[:, s0 - first : reach - first]
                         yh[:, reach:s1] = 0

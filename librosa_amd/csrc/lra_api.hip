@@ -42,6 +42,7 @@
 #include "lra_peaks_launch.h"
 #include "lra_chroma_launch.h"
 #include "lra_pitch_launch.h"
+#include "lra_yin_launch.h"
 
 using namespace lra;
 
@@ -3357,6 +3358,66 @@ int lra_pitch_tuning_exec(lra_ctx* ctx, const void* freq, int64_t n, int dtype, 
     const int64_t n_segments = (n + pitch::kPlainSeg - 1) / pitch::kPlainSeg;
     pitch::HistArgs h{freq, nullptr, nullptr, n_segments, n, pitch::kPlainSeg, nullptr, (const double*)edges, (int)n_hist, bins_per_octave, (unsigned long long*)out};
     LRA_HIP(pitch::launch_tuning_hist(h, dtype == LRA_F64, ctx->stream));
+    return LRA_OK;
+}
+
+// ---- yin and the front half of pyin (lra_yin.h, launched from lra_yin_inst.hip) ----------------------------------------------------------
+static_assert(yin::kF0 == LRA_YIN_F0 && yin::kFrames == LRA_YIN_FRAMES, "yin codes");
+static_assert(yin::transform_length(64, 27) == 160 && yin::transform_length(2048, 340) == 2400 && yin::transform_length(2048, 2047) == 4800 && yin::transform_length(4096, 705) == 0,
+              "yin transform lengths");
+
+int64_t lra_yin_lds_bytes(int frame_length, int max_period) {
+    if (frame_length < 1 || max_period < 1) return 0;
+    return yin::lds_layout(yin::transform_length(frame_length, max_period), max_period).total;
+}
+
+int lra_yin_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, int dtype, int frame_length, int hop_length, int center, int pad_mode, int min_period, int max_period,
+                 double trough_threshold, double sr, int mode, void* f0, void* frames, void* shifts) {
+    LRA_BIND(ctx);
+    if (mode != LRA_YIN_F0 && mode != LRA_YIN_FRAMES) return fail(LRA_EINVAL, "yin: unknown mode");
+    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "yin: dtype must be LRA_F32 or LRA_F64");
+    if (frame_length < 3 || hop_length < 1) return fail(LRA_EINVAL, "yin: frame_length must be at least 3 and hop_length positive");
+    if (pad_mode < 0 || pad_mode > 3) return fail(LRA_EINVAL, "yin: unknown pad mode");
+    if (min_period < 1 || max_period <= min_period || max_period > frame_length - 1) return fail(LRA_EINVAL, "yin: need 1 <= min_period < max_period <= frame_length - 1");
+    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "yin: negative size");
+    const int pad = center ? frame_length / 2 : 0;
+    if (n + 2 * (int64_t)pad < frame_length)
+        return fail(LRA_EINVAL, "yin: input is too short (n=" + std::to_string(n + 2 * (int64_t)pad) + ") for frame_length=" + std::to_string(frame_length));
+    const int64_t n_frames = 1 + (n + 2 * (int64_t)pad - frame_length) / hop_length;
+    if (batch == 0) return LRA_OK;
+    if (!y || (mode == LRA_YIN_F0 ? !f0 : (!frames || !shifts))) return fail(LRA_EINVAL, "null data pointer");
+    if (n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames per clip");
+    const int N = yin::transform_length(frame_length, max_period);
+    if (yin::lds_layout(N, max_period).total > yin::kYinLdsMax)
+        return fail(LRA_EINVAL, "yin: max_period=" + std::to_string(max_period) + " does not fit the LDS of a workgroup");
+    yin::Args a{};
+    a.y = y;
+    a.y_f64 = dtype == LRA_F64;
+    a.n = n;
+    a.n_frames = n_frames;
+    a.W = frame_length;
+    a.hop = hop_length;
+    a.pad = pad;
+    a.pad_mode = pad_mode;
+    a.N = N;
+    a.min_period = min_period;
+    a.max_period = max_period;
+    a.threshold = trough_threshold;
+    a.sr = sr;
+    a.tiny = 2.2250738585072014e-308;  // util.tiny of the float64 cumulative mean (the division by the int64 lags promotes a float32 frame)
+    if (N > 0) {
+        auto& tw = ctx->cqt_tw[std::make_pair(N, (int)LRA_F64)];
+        if (!tw.first) LRA_TRY(mixed_tables(N, LRA_F64, &tw.first, &tw.second));
+        a.tw_m = (const mixed::cpx<double>*)tw.first;
+        a.tw_n = (const mixed::cpx<double>*)tw.second;
+    }
+    a.mode = mode;
+    a.f0 = (double*)f0;
+    a.frames = frames;
+    a.shifts = shifts;
+    a.groups = (int)((n_frames + yin::kYinGroup - 1) / yin::kYinGroup);
+    if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames for one launch");
+    LRA_HIP(yin::launch_yin(a, batch, ctx->stream));
     return LRA_OK;
 }
 
