@@ -2,10 +2,9 @@
 
 The library holds several hundred instances of the fused kernels; hipcc compiles one translation unit on
 one core, so the instances are split into groups (``csrc/lra_fused.h``) that are compiled side by side:
-``lra_inst.hip`` once per group plus ``lra_api.hip`` (host API, general rocFFT path), ``lra_mixed_inst.hip`` and
-``lra_rhythm_inst.hip`` (the tempogram kernels), ``lra_beat_inst.hip`` (the beat tracker), ``lra_peaks_inst.hip``
-(the peak picker), ``lra_chroma_inst.hip`` (the chroma kernels) and ``lra_pitch_inst.hip`` (the pitch tracker and the tuning
-estimate) and ``lra_yin_inst.hip`` (YIN), then one link.  The
+``lra_inst.hip`` once per group plus the units of ``UNITS`` below -- ``lra_api.hip`` (host API, general rocFFT path) and one
+``lra_<feature>_inst.hip`` per family of kernels with a translation unit of its own (mixed-radix transforms, tempogram, beat
+tracker, peak picker, chroma, pitch tracker and tuning estimate, YIN) -- then one link.  The
 result ``librosa_amd/_liblibrosa_amd.so`` is git-ignored but travels to the GPU box with the repo snapshot.
 hipcc cross-compiles for gfx950 without a GPU.
 """
@@ -24,6 +23,9 @@ OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "_liblibrosa_amd.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# the translation units csrc/lra_<unit>.hip that are compiled once each (lra_inst.hip is compiled once per instance group besides);
+# scripts/device_asm_diff.sh reads this list
+UNITS = ("api", "mixed_inst", "rhythm_inst", "beat_inst", "peaks_inst", "chroma_inst", "pitch_inst", "yin_inst")
 
 
 def sources():
@@ -59,14 +61,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT):
     hipcc = os.path.join(ROCM, "bin", "hipcc")
     os.makedirs(OBJ, exist_ok=True)
     tag = "_" + str(abs(hash(tuple(extra_flags))) % 10**8) if extra_flags else ""
-    jobs = [([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_api.hip"), "-o", os.path.join(OBJ, f"api{tag}.o")])]
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_mixed_inst.hip"), "-o", os.path.join(OBJ, f"mixed{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_rhythm_inst.hip"), "-o", os.path.join(OBJ, f"rhythm{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_beat_inst.hip"), "-o", os.path.join(OBJ, f"beat{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_peaks_inst.hip"), "-o", os.path.join(OBJ, f"peaks{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_chroma_inst.hip"), "-o", os.path.join(OBJ, f"chroma{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_pitch_inst.hip"), "-o", os.path.join(OBJ, f"pitch{tag}.o")])
-    jobs.append([hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, "lra_yin_inst.hip"), "-o", os.path.join(OBJ, f"yin{tag}.o")])
+    jobs = [[hipcc, *FLAGS, *extra_flags, "-c", os.path.join(CSRC, f"lra_{u}.hip"), "-o", os.path.join(OBJ, f"{u.replace('_inst', '')}{tag}.o")] for u in UNITS]
     for g in range(n_groups()):
         jobs.append([hipcc, *FLAGS, *extra_flags, f"-DLRA_INST_GROUP={g}", "-c", os.path.join(CSRC, "lra_inst.hip"), "-o", os.path.join(OBJ, f"inst{tag}_{g}.o")])
 

@@ -282,7 +282,7 @@ struct lra_stft_plan {
     bool pow2 = false;
     int logm = 0;
     void* d_win = nullptr;
-    void* d_win_full = nullptr;  // powers of two in lra_mixed_launch.h's forward list: the window itself (d_win holds 0.5 x window there), for the flat-index mel kernel
+    void* d_win_full = nullptr;  // powers of two in lra_mixed_sizes.h's forward list: the window itself (d_win holds 0.5 x window there), for the flat-index mel kernel
     void* d_tw[kNumVariants] = {};
     int tuned_variant[4] = {-1, -1, -1, -1};  // per epilogue mode (autotune), -1 = not measured yet  // pass-twiddle tables; their layout depends on the kernel configuration
     void* d_twr = nullptr;
@@ -1131,7 +1131,7 @@ int stft_run(lra_stft_plan* p, int mode, const void* y, int64_t batch, int64_t n
         if (mel->n_bins != bins) return fail(LRA_EINVAL, "mel basis has " + std::to_string(mel->n_bins) + " bins, stft has " + std::to_string(bins));
         if (mel->dtype != p->dtype) return fail(LRA_EINVAL, "mel plan dtype differs from stft plan dtype");
     }
-    // (powers of two in lra_mixed_launch.h's forward list: the fused mel goes to the flat-index kernel further down, everything else stays here)
+    // (powers of two in lra_mixed_sizes.h's forward list: the fused mel goes to the flat-index kernel further down, everything else stays here)
     // where it wins, measured on 256 x 30 s: n_fft 256 from 56 bands (80 bands at hop 64: 2.02 -> 1.28 ms; 48 bands 0.92 against 1.15: stays), n_fft 128 from 40
     // (64 bands at hop 32: 3.63 -> 2.06; 32 bands 1.51 against 1.71: stays)
     const bool pow2_mel_mixed = p->pow2 && mode == OUT_MEL && p->d_mtw && ctx->opt_mixed && ctx->opt_mixed_pow2_mel && row_pitch == bins && mel &&
@@ -2273,22 +2273,16 @@ int lra_event_elapsed_ms(lra_event* start, lra_event* stop, float* ms) {
 
 // ---- STFT ---------------------------------------------------------------------------------------
 namespace {
-// twiddle tables of the mixed-radix kernels (lra_mixed.h): W_M^t, t < M, and W_N^k, k <= M, evaluated in double and rounded once
+// twiddle tables of the mixed-radix kernels on the device: mixed::fill_twiddles (lra_mixed.h), uploaded
 int mixed_tables(int n_fft, int dtype, void** d_mtw, void** d_mtwn) {
-    const int M = n_fft / 2;
-    const double two_pi = 6.283185307179586476925286766559;
-    if (dtype == LRA_F64) {
-        std::vector<cx<double>> t1(M), t2(M + 1);
-        for (int t = 0; t < M; ++t) t1[t] = mk<double>(std::cos(-two_pi * t / M), std::sin(-two_pi * t / M));
-        for (int k = 0; k <= M; ++k) t2[k] = mk<double>(std::cos(-two_pi * k / n_fft), std::sin(-two_pi * k / n_fft));
-        LRA_TRY(upload(d_mtw, t1.data(), t1.size() * sizeof(cx<double>)));
-        return upload(d_mtwn, t2.data(), t2.size() * sizeof(cx<double>));
-    }
-    std::vector<cx<float>> t1(M), t2(M + 1);
-    for (int t = 0; t < M; ++t) t1[t] = mk<float>((float)std::cos(-two_pi * t / M), (float)std::sin(-two_pi * t / M));
-    for (int k = 0; k <= M; ++k) t2[k] = mk<float>((float)std::cos(-two_pi * k / n_fft), (float)std::sin(-two_pi * k / n_fft));
-    LRA_TRY(upload(d_mtw, t1.data(), t1.size() * sizeof(cx<float>)));
-    return upload(d_mtwn, t2.data(), t2.size() * sizeof(cx<float>));
+    auto fill_and_upload = [&](auto real) -> int {
+        using T = decltype(real);
+        std::vector<mixed::cpx<T>> t1(n_fft / 2), t2(n_fft / 2 + 1);
+        mixed::fill_twiddles<T>(n_fft, t1.data(), t2.data());
+        LRA_TRY(upload(d_mtw, t1.data(), t1.size() * sizeof(mixed::cpx<T>)));
+        return upload(d_mtwn, t2.data(), t2.size() * sizeof(mixed::cpx<T>));
+    };
+    return dtype == LRA_F64 ? fill_and_upload(double()) : fill_and_upload(float());
 }
 }  // namespace
 
@@ -3010,41 +3004,30 @@ int lra_tempogram_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, 
     if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "tempogram: dtype must be LRA_F32 or LRA_F64");
     if (win_length < 1) return fail(LRA_EINVAL, "tempogram: win_length must be a positive integer");
     if (batch < 0 || n < 0) return fail(LRA_EINVAL, "tempogram: negative size");
-    const int pad = center ? win_length / 2 : 0;
-    if (n + 2 * (int64_t)pad < win_length)
-        return fail(LRA_EINVAL, "tempogram: input is too short (n=" + std::to_string(n + 2 * (int64_t)pad) + ") for frame_length=" + std::to_string(win_length));
-    const int64_t n_frames = center ? n : n - win_length + 1;
+    rhythm::Args a{};
+    const int geometry = rhythm::prepare(a, n, win_length, center, norm, mode);
+    if (geometry == mixed::kGeometryTooShort)
+        return fail(LRA_EINVAL, "tempogram: input is too short (n=" + std::to_string(n + 2 * (int64_t)a.pad) + ") for frame_length=" + std::to_string(win_length));
+    const int64_t n_frames = a.n_frames;
     if (batch == 0 || n_frames == 0) return LRA_OK;
     if (!env || !window || !out || !work) return fail(LRA_EINVAL, "null data pointer");
     if (mode != LRA_TEMPOGRAM_WRITE && (!logprior || !bpms)) return fail(LRA_EINVAL, "tempogram: tempo modes need the prior and the BPM table");
     if (n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames per clip");
-    const int N = rhythm::transform_length(win_length);
-    if (rhythm::lds_layout(N, win_length, mode, false).total > rhythm::kRhythmLdsMax)
-        return fail(LRA_EINVAL, "tempogram: win_length=" + std::to_string(win_length) + " does not fit the LDS of a workgroup");
-    rhythm::Args a{};
+    if (geometry == mixed::kGeometryLds) return fail(LRA_EINVAL, "tempogram: win_length=" + std::to_string(win_length) + " does not fit the LDS of a workgroup");
     a.env = env;
     a.env_f64 = dtype == LRA_F64;
-    a.n = n;
-    a.n_frames = n_frames;
-    a.W = win_length;
-    a.pad = pad;
-    a.N = N;
     a.win = (const double*)window;
-    if (N > 0) {
-        auto& tw = ctx->cqt_tw[std::make_pair(N, (int)LRA_F64)];
-        if (!tw.first) LRA_TRY(mixed_tables(N, LRA_F64, &tw.first, &tw.second));
+    if (a.N > 0) {
+        auto& tw = ctx->cqt_tw[std::make_pair(a.N, (int)LRA_F64)];
+        if (!tw.first) LRA_TRY(mixed_tables(a.N, LRA_F64, &tw.first, &tw.second));
         a.tw_m = (const mixed::cpx<double>*)tw.first;
         a.tw_n = (const mixed::cpx<double>*)tw.second;
     }
-    a.norm = norm;
-    a.mode = mode;
-    a.tile = mode == LRA_TEMPOGRAM_WRITE && rhythm::lds_layout(N, win_length, mode, true).total <= rhythm::kRhythmLdsMax;
     a.logprior = (const double*)logprior;
     a.bpms = (const double*)bpms;
     a.out = (double*)out;
     a.flag = (int*)work;
     a.partial = (double*)((char*)work + 16);
-    a.groups = (int)((n_frames + rhythm::kRhythmGroup - 1) / rhythm::kRhythmGroup);
     if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames for one launch");
     LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
     LRA_HIP(rhythm::launch_tempogram(a, batch, ctx->stream));
@@ -3380,42 +3363,25 @@ int lra_yin_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, int dtyp
     if (pad_mode < 0 || pad_mode > 3) return fail(LRA_EINVAL, "yin: unknown pad mode");
     if (min_period < 1 || max_period <= min_period || max_period > frame_length - 1) return fail(LRA_EINVAL, "yin: need 1 <= min_period < max_period <= frame_length - 1");
     if (batch < 0 || n < 0) return fail(LRA_EINVAL, "yin: negative size");
-    const int pad = center ? frame_length / 2 : 0;
-    if (n + 2 * (int64_t)pad < frame_length)
-        return fail(LRA_EINVAL, "yin: input is too short (n=" + std::to_string(n + 2 * (int64_t)pad) + ") for frame_length=" + std::to_string(frame_length));
-    const int64_t n_frames = 1 + (n + 2 * (int64_t)pad - frame_length) / hop_length;
+    yin::Args a{};
+    const int geometry = yin::prepare(a, n, frame_length, hop_length, center, pad_mode, min_period, max_period, trough_threshold, sr, mode);
+    if (geometry == mixed::kGeometryTooShort)
+        return fail(LRA_EINVAL, "yin: input is too short (n=" + std::to_string(n + 2 * (int64_t)a.pad) + ") for frame_length=" + std::to_string(frame_length));
     if (batch == 0) return LRA_OK;
     if (!y || (mode == LRA_YIN_F0 ? !f0 : (!frames || !shifts))) return fail(LRA_EINVAL, "null data pointer");
-    if (n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames per clip");
-    const int N = yin::transform_length(frame_length, max_period);
-    if (yin::lds_layout(N, max_period).total > yin::kYinLdsMax)
-        return fail(LRA_EINVAL, "yin: max_period=" + std::to_string(max_period) + " does not fit the LDS of a workgroup");
-    yin::Args a{};
+    if (a.n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames per clip");
+    if (geometry == mixed::kGeometryLds) return fail(LRA_EINVAL, "yin: max_period=" + std::to_string(max_period) + " does not fit the LDS of a workgroup");
     a.y = y;
     a.y_f64 = dtype == LRA_F64;
-    a.n = n;
-    a.n_frames = n_frames;
-    a.W = frame_length;
-    a.hop = hop_length;
-    a.pad = pad;
-    a.pad_mode = pad_mode;
-    a.N = N;
-    a.min_period = min_period;
-    a.max_period = max_period;
-    a.threshold = trough_threshold;
-    a.sr = sr;
-    a.tiny = 2.2250738585072014e-308;  // util.tiny of the float64 cumulative mean (the division by the int64 lags promotes a float32 frame)
-    if (N > 0) {
-        auto& tw = ctx->cqt_tw[std::make_pair(N, (int)LRA_F64)];
-        if (!tw.first) LRA_TRY(mixed_tables(N, LRA_F64, &tw.first, &tw.second));
+    if (a.N > 0) {
+        auto& tw = ctx->cqt_tw[std::make_pair(a.N, (int)LRA_F64)];
+        if (!tw.first) LRA_TRY(mixed_tables(a.N, LRA_F64, &tw.first, &tw.second));
         a.tw_m = (const mixed::cpx<double>*)tw.first;
         a.tw_n = (const mixed::cpx<double>*)tw.second;
     }
-    a.mode = mode;
     a.f0 = (double*)f0;
     a.frames = frames;
     a.shifts = shifts;
-    a.groups = (int)((n_frames + yin::kYinGroup - 1) / yin::kYinGroup);
     if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames for one launch");
     LRA_HIP(yin::launch_yin(a, batch, ctx->stream));
     return LRA_OK;
@@ -3429,29 +3395,23 @@ int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch,
     if (n_in <= 0) return fail(LRA_EINVAL, "fir_decimate: empty input");
     if (!x || !out || !taps) return fail(LRA_EINVAL, "null data pointer");
     if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "fir_decimate: dtype must be LRA_F32 or LRA_F64");
-    const size_t elem = dtype == LRA_F64 ? 8 : 4;
-    // The selection below exists in three copies that have to stay in step: here, fir_route() of tests/hostsim/postsim.cpp (what the host simulator
-    // runs) and route() of tests/resample_cases.py (what the device tests expect each case to exercise; tests/test_resample_host.py compares the two).
-    // four outputs per thread (four independent chains, a quarter of the workgroups) where the longer span still fits 32 KB of LDS and the job is big
-    const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
-    const int opt = four ? 4 : 1;
-    const long long blocks_per_clip = (n_out + 256 * opt - 1) / (256 * opt);
+    const FirPlan plan = fir_plan(n_out, n_taps, down, dtype == LRA_F64 ? 8 : 4);  // the kernel and its geometry (lra_cqt.h)
+    const bool four = plan.opt == 4;
+    const long long blocks_per_clip = plan.blocks_per_clip;
+    const size_t lds = plan.lds_bytes;
     if (blocks_per_clip * batch > 0x7fffffffLL) return fail(LRA_EINVAL, "fir_decimate: array too large for one launch");
-    const size_t span2 = (size_t)1023 * 2 + n_taps;
-    const size_t lds2 = (span2 + span2 / 8 + 1) * 2 * elem;  // (sample, sample + 2) pairs, one pad entry per eight
-    if (four && down == 2 && lds2 <= 64 * 1024) {  // the octave recursion's halving: four consecutive outputs per thread, padded span of pairs (fir_halve4_kernel)
-        const unsigned grid2 = (unsigned)(blocks_per_clip * batch);
+    const unsigned grid = (unsigned)(blocks_per_clip * batch);
+    if (plan.route == kFirHalve4) {  // the octave recursion's halving: four consecutive outputs per thread, padded span of pairs
         if (dtype == LRA_F64)
-            hipLaunchKernelGGL(fir_halve4_kernel<double>, dim3(grid2), dim3(256), lds2, ctx->stream, (const double*)x, (double*)out, (const double*)taps, (long long)n_in, (long long)n_out,
+            hipLaunchKernelGGL(fir_halve4_kernel<double>, dim3(grid), dim3(256), lds, ctx->stream, (const double*)x, (double*)out, (const double*)taps, (long long)n_in, (long long)n_out,
                                (int)blocks_per_clip, n_taps, first, div, mul);
         else
-            hipLaunchKernelGGL(fir_halve4_kernel<float>, dim3(grid2), dim3(256), lds2, ctx->stream, (const float*)x, (float*)out, (const float*)taps, (long long)n_in, (long long)n_out,
+            hipLaunchKernelGGL(fir_halve4_kernel<float>, dim3(grid), dim3(256), lds, ctx->stream, (const float*)x, (float*)out, (const float*)taps, (long long)n_in, (long long)n_out,
                                (int)blocks_per_clip, n_taps, first, div, mul);
         LRA_HIP(hipGetLastError());
         return LRA_OK;
     }
-    const size_t lds = ((size_t)(256 * opt - 1) * down + n_taps) * elem;  // the workgroup's input span
-    if (lds > 64 * 1024) {  // span too long to stage: the direct kernel
+    if (plan.route == kFirDirect) {  // span too long to stage
         const long long count = (long long)batch * n_out;
         if ((count + 255) / 256 > 0x7fffffffLL) return fail(LRA_EINVAL, "fir_decimate: array too large for one launch");
         const unsigned dgrid = (unsigned)((count + 255) / 256);
@@ -3464,8 +3424,7 @@ int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch,
         LRA_HIP(hipGetLastError());
         return LRA_OK;
     }
-    const unsigned grid = (unsigned)(blocks_per_clip * batch);
-#define LRA_FIR(T, OPT)                                                                                                                                                            \
+#define LRA_FIR(T, OPT)                                                                                                                                                           \
     hipLaunchKernelGGL((fir_decimate_kernel<T, OPT>), dim3(grid), dim3(256), lds, ctx->stream, (const T*)x, (T*)out, (const T*)taps, (long long)n_in, (long long)n_out, (int)blocks_per_clip, \
                        n_taps, down, first, div, mul)
     if (dtype == LRA_F64) { if (four) LRA_FIR(double, 4); else LRA_FIR(double, 1); }

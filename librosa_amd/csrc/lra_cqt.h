@@ -10,6 +10,7 @@
 #ifndef LRA_POSTSIM
 #include <hip/hip_runtime.h>
 #endif
+#include <cstddef>
 
 namespace lra {
 
@@ -295,6 +296,41 @@ __global__ __launch_bounds__(256) void fir_halve4_kernel(const T* __restrict__ x
             out[clip * n_out + n] = mul == 1.0 ? scaled : (T)((double)scaled * mul);
         }
     }
+}
+
+// Host: which of the four FIR kernels above serves a job, and its launch geometry -- what lra_fir_decimate_exec (lra_api.hip) launches and what the
+// host simulator (tests/hostsim/postsim.cpp) runs.  tests/resample_cases.py::route() restates the selection as the tests' independent expectation
+// (tests/test_resample_host.py holds this function to it): two copies that have to stay in step.
+//   four outputs per thread (four independent chains, a quarter of the workgroups) where the longer span still fits 32 KB of LDS and the job is big;
+//   of those the octave recursion's halving (down == 2) takes fir_halve4_kernel where its padded span of pairs fits 64 KB;
+//   one output per thread otherwise, and the direct kernel where even that span is too long to stage.
+enum FirRoute { kFirHalve4 = 0, kFirOpt4 = 1, kFirOpt1 = 2, kFirDirect = 3 };
+struct FirPlan {
+    FirRoute route;
+    int opt;                    // outputs per thread: 4 (halve4, opt4) or 1
+    long long blocks_per_clip;  // workgroups of 256 opt outputs per clip (direct: its grid is ceil(batch n_out / 256) instead)
+    size_t lds_bytes;           // dynamic LDS of the launch (direct: none)
+};
+inline FirPlan fir_plan(long long n_out, int n_taps, int down, int elem_bytes) {
+    const size_t elem = (size_t)elem_bytes;
+    const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
+    FirPlan p;
+    p.opt = four ? 4 : 1;
+    p.blocks_per_clip = (n_out + 256 * p.opt - 1) / (256 * p.opt);
+    const size_t span2 = (size_t)1023 * 2 + n_taps;
+    const size_t lds2 = (span2 + span2 / 8 + 1) * 2 * elem;  // (sample, sample + 2) pairs, one pad entry per eight
+    const size_t lds = ((size_t)(256 * p.opt - 1) * down + n_taps) * elem;  // the workgroup's input span
+    if (four && down == 2 && lds2 <= 64 * 1024) {
+        p.route = kFirHalve4;
+        p.lds_bytes = lds2;
+    } else if (lds > 64 * 1024) {
+        p.route = kFirDirect;
+        p.lds_bytes = 0;
+    } else {
+        p.route = four ? kFirOpt4 : kFirOpt1;
+        p.lds_bytes = lds;
+    }
+    return p;
 }
 
 // ---- sparse basis projection: fft_basis.dot(D) of __cqt_response (constantq.py:1213-1218) and the length scaling (:1116-1118),

@@ -23,6 +23,7 @@
 #ifndef LRA_POSTSIM
 #include <hip/hip_runtime.h>
 #endif
+#include <cmath>
 
 // (no wave priorities here: s_setprio per stage -- frame loads, passes, split, mel reduce -- moved nothing, profiles/r04_experiments.md 10)
 
@@ -42,6 +43,24 @@ __device__ __forceinline__ double fma_t(double a, double b, double c) { return _
 template <class T> __device__ __forceinline__ cpx<T> mul(cpx<T> a, cpx<T> b) { return mkc<T>(fma_t(-a.y, b.y, a.x * b.x), fma_t(a.y, b.x, a.x * b.y)); }
 template <class T> __device__ __forceinline__ cpx<T> mul_mi(cpx<T> a) { return mkc<T>(a.y, -a.x); }  // a * (-i)
 template <class T> __device__ __forceinline__ cpx<T> scale(cpx<T> a, T k) { return mkc<T>(a.x * k, a.y * k); }
+
+// Host: the twiddle tables of a transform of length n_fft = 2 M -- tw_m[t] = W_M^t, t < M, and tw_n[k] = W_N^k, k <= M -- evaluated in double
+// and rounded once.  The one place they are computed: lra_api.hip uploads them, the host simulators hand them to the same kernel bodies.
+template <class T> inline void fill_twiddles(int n_fft, cpx<T>* tw_m, cpx<T>* tw_n) {
+    const int M = n_fft / 2;
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int t = 0; t < M; ++t) {
+        tw_m[t].x = (T)std::cos(-two_pi * t / M);
+        tw_m[t].y = (T)std::sin(-two_pi * t / M);
+    }
+    for (int k = 0; k <= M; ++k) {
+        tw_n[k].x = (T)std::cos(-two_pi * k / n_fft);
+        tw_n[k].y = (T)std::sin(-two_pi * k / n_fft);
+    }
+}
+
+// what a feature's host-side geometry function (rhythm::prepare, yin::prepare) answers
+enum { kGeometryOk = 0, kGeometryTooShort = 1, kGeometryLds = 2 };
 
 // ---- factorisation of M (compile time) ---------------------------------------------------------------------------------------
 struct Radices {

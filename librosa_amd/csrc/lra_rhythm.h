@@ -28,6 +28,7 @@
 #endif
 
 #include "lra_mixed.h"
+#include "lra_mixed_sizes.h"
 
 #ifdef LRA_POSTSIM
 #define LRA_RHYTHM_DYN_LDS(ptr) char* ptr = reinterpret_cast<char*>(g_postsim_dyn_lds)
@@ -94,6 +95,26 @@ struct Args {
     int* flag;               // set to 1 where a column is not finite
     int groups;              // ceil(n_frames / kRhythmGroup)
 };
+
+// the smallest size of LRA_MIXED_SIZES that holds the linear autocorrelation of W samples (2 W - 1), or 0: the direct kernel
+constexpr int transform_length(int W) { return mixed::smallest_size_at_least(2 * W - 1); }
+
+// Host: the geometry of one lra_tempogram_exec call, from its scalar parameters into a (the pointers and env_f64 stay the caller's).  Answers
+// mixed::kGeometryTooShort (only W and pad set: the padded envelope does not hold one frame) or, everything set, mixed::kGeometryLds (no kernel fits
+// the LDS of a workgroup for this W).  direct: the O(W^2) kernel whatever the size list offers -- the host simulator's switch.
+inline int prepare(Args& a, long long n, int W, int center, int norm, int mode, bool direct = false) {
+    a.W = W;
+    a.pad = center ? W / 2 : 0;
+    if (n + 2 * (long long)a.pad < W) return mixed::kGeometryTooShort;
+    a.n = n;
+    a.n_frames = center ? n : n - W + 1;
+    a.N = direct ? 0 : transform_length(W);
+    a.norm = norm;
+    a.mode = mode;
+    a.tile = mode == kWrite && lds_layout(a.N, W, mode, true).total <= kRhythmLdsMax;
+    a.groups = (int)((a.n_frames + kRhythmGroup - 1) / kRhythmGroup);
+    return lds_layout(a.N, W, mode, false).total > kRhythmLdsMax ? mixed::kGeometryLds : mixed::kGeometryOk;
+}
 
 // padded position q of a clip: np.pad(mode="linear_ramp", end_values=0) builds each ramp with np.linspace(0, edge, pad, endpoint=False)
 // in float64 -- i * (edge / pad) -- and rounds it once to the envelope's dtype; the right ramp is the reversed one
@@ -219,7 +240,7 @@ __device__ __forceinline__ void rhythm_finish_group(const Args& a, char* lds, co
     }
 }
 
-// the transform of length N (in lra_mixed_launch.h's size list)
+// the transform of length N (in lra_mixed_sizes.h's size list)
 template <int N> __device__ __forceinline__ void tempogram_fft_body(const Args& a) {
     constexpr int M = N / 2, FC = chunk_frames<N>(), HP = M / 2 + 1;
     LRA_RHYTHM_DYN_LDS(lds);

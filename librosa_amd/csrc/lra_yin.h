@@ -33,6 +33,7 @@
 #endif
 
 #include "lra_mixed.h"
+#include "lra_mixed_sizes.h"
 
 #ifdef LRA_POSTSIM
 #define LRA_YIN_DYN_LDS(ptr) char* ptr = reinterpret_cast<char*>(g_postsim_dyn_lds)
@@ -92,6 +93,31 @@ struct Args {
     void* shifts;            // FRAMES: the same shape
     int groups;              // ceil(n_frames / kYinGroup)
 };
+
+// the smallest size of LRA_MIXED_SIZES that holds the linear autocorrelation of W samples up to lag P (W + P), or 0: the direct kernel
+constexpr int transform_length(int W, int P) { return mixed::smallest_size_at_least(W + P); }
+
+// Host: the geometry of one lra_yin_exec call, from its scalar parameters into a (the pointers and y_f64 stay the caller's).  Answers
+// mixed::kGeometryTooShort (only W, hop and pad set: the padded clip does not hold one frame) or, everything set, mixed::kGeometryLds (max_period
+// does not fit the LDS of a workgroup).  direct: the direct kernel whatever the size list offers -- the host simulator's switch.
+inline int prepare(Args& a, long long n, int W, int hop, int center, int pad_mode, int min_period, int max_period, double threshold, double sr, int mode, bool direct = false) {
+    a.W = W;
+    a.hop = hop;
+    a.pad = center ? W / 2 : 0;
+    if (n + 2 * (long long)a.pad < W) return mixed::kGeometryTooShort;
+    a.n = n;
+    a.n_frames = 1 + (n + 2 * (long long)a.pad - W) / hop;
+    a.pad_mode = pad_mode;
+    a.N = direct ? 0 : transform_length(W, max_period);
+    a.min_period = min_period;
+    a.max_period = max_period;
+    a.threshold = threshold;
+    a.sr = sr;
+    a.tiny = 2.2250738585072014e-308;  // util.tiny of the float64 cumulative mean (the division by the int64 lags promotes a float32 frame)
+    a.mode = mode;
+    a.groups = (int)((a.n_frames + kYinGroup - 1) / kYinGroup);
+    return lds_layout(a.N, max_period).total > kYinLdsMax ? mixed::kGeometryLds : mixed::kGeometryOk;
+}
 
 // sample q of the padded clip (np.pad's modes as lra::mixed::fetch)
 __device__ __forceinline__ double yin_sample(const Args& a, long long clip, long long q) {
@@ -216,7 +242,7 @@ __device__ __forceinline__ void yin_finish(const Args& a, char* lds, const Lds& 
     __syncthreads();
 }
 
-// the transform of length N (in lra_mixed_launch.h's size list), N >= W + max_period
+// the transform of length N (in lra_mixed_sizes.h's size list), N >= W + max_period
 template <int N> __device__ __forceinline__ void yin_fft_body(const Args& a) {
     constexpr int M = N / 2, FC = chunk_frames<N>(), HP = M / 2 + 1, IT = (FC * M + kYinNT - 1) / kYinNT;
     LRA_YIN_DYN_LDS(lds);

@@ -10,8 +10,8 @@ work=${WORK:-$(mktemp -d)}
 [ -n "${WORK:-}" ] || trap 'rm -rf "$work"' EXIT  # (a directory of our own making goes again)
 hipcc=${ROCM_PATH:-/opt/rocm}/bin/hipcc
 flags="--offload-arch=gfx950 -O3 -std=c++17 -fPIC --cuda-device-only -S -Wno-unused-command-line-argument"
-groups=$(sed -n 's/^#define LRA_INST_NUM_GROUPS \([0-9]*\).*/\1/p' "$root/librosa_amd/csrc/lra_fused.h")
-units="api mixed_inst rhythm_inst beat_inst peaks_inst chroma_inst $(seq -f inst:%g 0 $((groups - 1)))"
+# the working tree's list of translation units (librosa_amd/build.py) and its instance groups
+units=$(cd "$root" && python -c "from librosa_amd.build import UNITS, n_groups; print(*UNITS, *(f'inst:{g}' for g in range(n_groups())))")
 
 mkdir -p "$work/parent" "$work/new"
 [ -d "$work/parent/librosa_amd" ] || git -C "$root" archive "$rev" librosa_amd/csrc include | tar -x -C "$work/parent"

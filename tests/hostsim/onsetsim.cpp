@@ -1,85 +1,13 @@
-// onsetsim.cpp -- runs the onset-strength kernel bodies of librosa_amd/csrc/lra_onset.h on host threads.
+// onsetsim.cpp -- runs the onset-strength kernel bodies of librosa_amd/csrc/lra_onset.h on host threads (tests/hostsim/simshim.h).
 //
-// TEST INFRASTRUCTURE ONLY.  Built by tests/test_onset_host.py (g++ -DLRA_POSTSIM -pthread) into tests/hostsim/_onsetsim.so.  One OS
-// thread per lane of a workgroup, __syncthreads() is a barrier across them, __shared__ is a static the lanes share; workgroups run one
-// after the other.  Never linked into, imported by, or used as a fallback for the product library.
-#define LRA_POSTSIM 1
-#include <cmath>
-#include <condition_variable>
-#include <cstddef>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-struct SimIdx { unsigned x = 0, y = 0, z = 0; };
-static thread_local SimIdx threadIdx;
-static thread_local SimIdx blockIdx;
-static thread_local SimIdx blockDim;
-
-namespace {
-struct Barrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int n = 0, waiting = 0;
-    unsigned long long gen = 0;
-    void wait() {
-        std::unique_lock<std::mutex> lk(m);
-        const unsigned long long g = gen;
-        if (++waiting == n) {
-            waiting = 0;
-            ++gen;
-            cv.notify_all();
-        } else {
-            cv.wait(lk, [&] { return gen != g; });
-        }
-    }
-};
-Barrier g_barrier;
-}  // namespace
-static inline void __syncthreads() { g_barrier.wait(); }
-
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(...)
-using std::exp;
-using std::expm1;
-using std::log;
-using std::log10;
-using std::log1p;
-using std::pow;
-
-alignas(16) static unsigned char g_postsim_dyn_lds[160 * 1024];  // the dynamic LDS of the workgroup being run
+// TEST INFRASTRUCTURE ONLY.  Built by tests/hostsim_util.py (sim_lib) into tests/hostsim/_onsetsim.so.
+// Never linked into, imported by, or used as a fallback for the product library.
+#define LRA_SIM_THREADS 1
+#include "simshim.h"
 
 #include "../../librosa_amd/csrc/lra_onset.h"
 
 namespace {
-template <class F> void run_grid(unsigned grid, unsigned block, F body) {
-    g_barrier.n = (int)block;
-    for (unsigned b = 0; b < grid; ++b) {
-        std::vector<std::thread> lanes;
-        for (unsigned t = 0; t < block; ++t)
-            lanes.emplace_back([=] {
-                threadIdx.x = t;
-                blockIdx.x = b;
-                blockDim.x = block;
-                body();
-            });
-        for (auto& l : lanes) l.join();
-    }
-}
-// kernels without __syncthreads (each lane owns its LDS column): the lanes of a workgroup one after the other on the calling thread
-template <class F> void run_grid_serial(unsigned grid, unsigned block, F body) {
-    for (unsigned b = 0; b < grid; ++b)
-        for (unsigned t = 0; t < block; ++t) {
-            threadIdx.x = t;
-            blockIdx.x = b;
-            blockDim.x = block;
-            body();
-        }
-}
-
 // the launches of onset_run (lra_api.hip): same geometry, same kernel selection
 template <class T, bool DB>
 int sim_run(lra::OnsetArgs<T> a, int aggregate, int max_ch_bands, int detrend, void* env, void* out) {

@@ -1,85 +1,20 @@
-// peaksim.cpp -- runs the peak-picking kernel bodies of librosa_amd/csrc/lra_peaks.h on host threads.
+// peaksim.cpp -- runs the peak-picking kernel bodies of librosa_amd/csrc/lra_peaks.h on host threads (tests/hostsim/simshim.h).
 //
-// TEST INFRASTRUCTURE ONLY.  Built by tests/test_peaks_host.py (g++ -DLRA_POSTSIM -pthread) into tests/hostsim/_peaksim.so.  One OS thread per
-// lane of a workgroup, __syncthreads() is a barrier across them, __shared__ is a static the lanes share; workgroups run one after the other.
-// The kernel's ballot is a stand-in here: every lane posts its flag, a barrier, every lane reads all of them.
+// TEST INFRASTRUCTURE ONLY.  Built by tests/hostsim_util.py (sim_lib) into tests/hostsim/_peaksim.so.
 // Never linked into, imported by, or used as a fallback for the product library.
 // With -DPEAKSIM_MAIN the file is a program of its own (a few fixed rows through every kernel), for a stand-alone sanitizer build.
-#define LRA_POSTSIM 1
-#include <cmath>
-#include <condition_variable>
-#include <cstddef>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-struct SimIdx { unsigned x = 0, y = 0, z = 0; };
-static thread_local SimIdx threadIdx;
-static thread_local SimIdx blockIdx;
-static thread_local SimIdx blockDim;
-
-namespace {
-struct Barrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int n = 0, waiting = 0;
-    unsigned long long gen = 0;
-    void wait() {
-        std::unique_lock<std::mutex> lk(m);
-        const unsigned long long g = gen;
-        if (++waiting == n) {
-            waiting = 0;
-            ++gen;
-            cv.notify_all();
-        } else {
-            cv.wait(lk, [&] { return gen != g; });
-        }
-    }
-};
-Barrier g_barrier;
-int g_lane_flag[64];
-}  // namespace
-static inline void __syncthreads() { g_barrier.wait(); }
-
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(...)
+#define LRA_SIM_THREADS 1
+#include "simshim.h"
 
 namespace lra {
 namespace peaks {
-unsigned long long peaks_wave_ballot(int pred) {
-    g_lane_flag[threadIdx.x] = pred != 0;
-    __syncthreads();
-    unsigned long long b = 0;
-    for (int l = 0; l < 64; ++l) b |= (unsigned long long)(g_lane_flag[l] != 0) << l;
-    __syncthreads();
-    return b;
-}
+unsigned long long peaks_wave_ballot(int pred) { return sim::wave_ballot(pred); }
 }  // namespace peaks
 }  // namespace lra
 
 #include "../../librosa_amd/csrc/lra_peaks.h"
 
 namespace {
-template <class F> void run_grid(unsigned grid, unsigned block, F body) {
-    g_barrier.n = (int)block;
-    for (unsigned b = 0; b < grid; ++b) {
-        std::vector<std::thread> lanes;
-        for (unsigned t = 0; t < block; ++t)
-            lanes.emplace_back([=] {
-                threadIdx.x = t;
-                blockIdx.x = b;
-                blockDim.x = block;
-                body();
-            });
-        for (auto& l : lanes) l.join();
-    }
-}
-
 template <class T> void run_pick(const lra::peaks::Args& a, long long batch) {
     using namespace lra::peaks;
     run_grid((unsigned)batch, kStatsNT, [=] { peak_stats_kernel<T>(a); });

@@ -1,87 +1,16 @@
 // postsim.cpp -- runs the PCEN / band max-filter kernel bodies of librosa_amd/csrc/lra_pcen.h and the constant-Q kernels of lra_cqt.h on
-// host threads.
+// host threads (tests/hostsim/simshim.h), and the HPSS, mixed-radix and random-number kernels likewise.
 //
-// TEST INFRASTRUCTURE ONLY.  Built by tests/test_hostsim.py (g++ -DLRA_POSTSIM -pthread) into tests/hostsim/_postsim.so.  One OS
-// thread per lane of a workgroup, __syncthreads() is a barrier across them, __shared__ is a static the lanes share; workgroups run
-// one after the other.  Never linked into, imported by, or used as a fallback for the product library.
-#define LRA_POSTSIM 1
-#include <cmath>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-struct SimIdx { unsigned x = 0, y = 0, z = 0; };
-static thread_local SimIdx threadIdx;
-static thread_local SimIdx blockIdx;
-
-namespace {
-struct Barrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int n = 0, waiting = 0;
-    unsigned long long gen = 0;
-    void wait() {
-        std::unique_lock<std::mutex> lk(m);
-        const unsigned long long g = gen;
-        if (++waiting == n) {
-            waiting = 0;
-            ++gen;
-            cv.notify_all();
-        } else {
-            cv.wait(lk, [&] { return gen != g; });
-        }
-    }
-};
-Barrier g_barrier;
-}  // namespace
-static inline void __syncthreads() { g_barrier.wait(); }
-
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(...)
-using std::exp;
-using std::expm1;
-using std::log;
-using std::log1p;
-using std::hypot;
-using std::pow;
-using std::sqrt;
-
-alignas(16) static unsigned char g_postsim_dyn_lds[160 * 1024];  // the dynamic LDS of the workgroup being run
+// TEST INFRASTRUCTURE ONLY.  Built by tests/hostsim_util.py (sim_lib) into tests/hostsim/_postsim.so.
+// Never linked into, imported by, or used as a fallback for the product library.
+#define LRA_SIM_THREADS 1
+#include "simshim.h"
 
 #include "../../librosa_amd/csrc/lra_pcen.h"
 #include "../../librosa_amd/csrc/lra_cqt.h"
 #include "../../librosa_amd/csrc/lra_hpss.h"
 #include "../../librosa_amd/csrc/lra_mixed.h"
 #include "../../librosa_amd/csrc/lra_rng.h"
-
-namespace {
-template <class F> void run_grid(unsigned grid, unsigned block, F body) {
-    g_barrier.n = (int)block;
-    for (unsigned b = 0; b < grid; ++b) {
-        std::vector<std::thread> lanes;
-        for (unsigned t = 0; t < block; ++t)
-            lanes.emplace_back([=] {
-                threadIdx.x = t;
-                blockIdx.x = b;
-                body();
-            });
-        for (auto& l : lanes) l.join();
-    }
-}
-// kernels without __syncthreads: the lanes of a workgroup one after the other on the calling thread
-template <class F> void run_grid_serial(unsigned grid, unsigned block, F body) {
-    for (unsigned b = 0; b < grid; ++b)
-        for (unsigned t = 0; t < block; ++t) {
-            threadIdx.x = t;
-            blockIdx.x = b;
-            body();
-        }
-}
-}  // namespace
 
 namespace {
 template <class T> void sim_hpss(const void* mag, const void* D, void* out_h, void* out_p, const lra::HpssArgs& a, unsigned grid) {
@@ -160,32 +89,28 @@ int postsim_resample_poly(const void* x, void* out, long long batch, long long n
     return 0;
 }
 
-// The kernel lra_fir_decimate_exec (lra_api.hip) selects, repeated by hand: four outputs per thread for big jobs whose span fits (the halving form where down == 2
-// and its padded span of pairs fits too), else one; the direct kernel for spans beyond the LDS.  tests/resample_cases.py::route() is the third copy;
-// tests/test_resample_host.py holds this one to it.
-enum FirRoute { kFirHalve4 = 0, kFirOpt4 = 1, kFirOpt1 = 2, kFirDirect = 3 };
-static FirRoute fir_route(long long n_out, int n_taps, int down, size_t elem) {
-    const bool four = n_out >= 8192 && ((size_t)(1023 * (long long)down + n_taps)) * elem <= 32 * 1024;
-    const size_t span2 = (size_t)1023 * 2 + n_taps;
-    if (four && down == 2 && (span2 + span2 / 8 + 1) * 2 * elem <= 64 * 1024) return kFirHalve4;
-    if (four) return kFirOpt4;
-    return ((size_t)(255 * (long long)down + n_taps)) * elem > 64 * 1024 ? kFirDirect : kFirOpt1;
+// what lra::fir_plan (lra_cqt.h: the library's own selection) answers: its route, or out = {route, outputs per thread, blocks per clip, LDS bytes}
+int postsim_fir_route(long long n_out, int n_taps, int down, int is_f64) { return (int)lra::fir_plan(n_out, n_taps, down, is_f64 ? 8 : 4).route; }
+void postsim_fir_plan(long long n_out, int n_taps, int down, int is_f64, long long* out) {
+    const lra::FirPlan p = lra::fir_plan(n_out, n_taps, down, is_f64 ? 8 : 4);
+    out[0] = p.route;
+    out[1] = p.opt;
+    out[2] = p.blocks_per_clip;
+    out[3] = (long long)p.lds_bytes;
 }
-int postsim_fir_route(long long n_out, int n_taps, int down, int is_f64) { return (int)fir_route(n_out, n_taps, down, is_f64 ? 8 : 4); }
 
 // the launches of lra_fir_decimate_exec / lra_cqt_project_exec (lra_api.hip)
 int postsim_fir_decimate(const void* x, void* out, long long batch, long long n_in, long long n_out, const void* taps, int n_taps, int down, int first, double div, double mul, int is_f64) {
-    const FirRoute route = fir_route(n_out, n_taps, down, is_f64 ? 8 : 4);
-    const bool four = route == kFirHalve4 || route == kFirOpt4;
-    const int opt = four ? 4 : 1;
-    const int blocks_per_clip = (int)((n_out + 256 * opt - 1) / (256 * opt));
-    if (route == kFirHalve4) {
-        const unsigned grid2 = (unsigned)(blocks_per_clip * batch);
-        if (is_f64) run_grid(grid2, 256, [=] { lra::fir_halve4_kernel<double>((const double*)x, (double*)out, (const double*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
-        else run_grid(grid2, 256, [=] { lra::fir_halve4_kernel<float>((const float*)x, (float*)out, (const float*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
+    const lra::FirPlan plan = lra::fir_plan(n_out, n_taps, down, is_f64 ? 8 : 4);
+    const bool four = plan.opt == 4;
+    const int blocks_per_clip = (int)plan.blocks_per_clip;
+    const unsigned grid = (unsigned)(blocks_per_clip * batch);
+    if (plan.route == lra::kFirHalve4) {
+        if (is_f64) run_grid(grid, 256, [=] { lra::fir_halve4_kernel<double>((const double*)x, (double*)out, (const double*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
+        else run_grid(grid, 256, [=] { lra::fir_halve4_kernel<float>((const float*)x, (float*)out, (const float*)taps, n_in, n_out, blocks_per_clip, n_taps, first, div, mul); });
         return 0;
     }
-    if (route == kFirDirect) {
+    if (plan.route == lra::kFirDirect) {
         const unsigned dgrid = (unsigned)((batch * n_out + 255) / 256);
         if (is_f64)
             run_grid_serial(dgrid, 256, [=] { lra::fir_decimate_direct_kernel<double>((const double*)x, (double*)out, (const double*)taps, batch, n_in, n_out, n_taps, down, first, div, mul); });
@@ -193,7 +118,6 @@ int postsim_fir_decimate(const void* x, void* out, long long batch, long long n_
             run_grid_serial(dgrid, 256, [=] { lra::fir_decimate_direct_kernel<float>((const float*)x, (float*)out, (const float*)taps, batch, n_in, n_out, n_taps, down, first, div, mul); });
         return 0;
     }
-    const unsigned grid = (unsigned)(blocks_per_clip * batch);
 #define SIM_FIR(T, OPT) run_grid(grid, 256, [=] { lra::fir_decimate_kernel<T, OPT>((const T*)x, (T*)out, (const T*)taps, n_in, n_out, blocks_per_clip, n_taps, down, first, div, mul); })
     if (is_f64) { if (four) SIM_FIR(double, 4); else SIM_FIR(double, 1); }
     else { if (four) SIM_FIR(float, 4); else SIM_FIR(float, 1); }

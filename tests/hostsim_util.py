@@ -19,12 +19,27 @@ CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 PAD_MODES = {"constant": 0, "reflect": 1, "edge": 2, "symmetric": 3}
 
 
-def _stale():
-    if not os.path.exists(SO):
+def _stale(so=SO, src=SRC):
+    """True where `so` is missing or older than its source, any tests/hostsim/*.h or any csrc/*.h."""
+    if not os.path.exists(so):
         return True
-    t = os.path.getmtime(SO)
-    deps = [SRC] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    t = os.path.getmtime(so)
+    deps = [src] + [os.path.join(d, f) for d in (CSRC, os.path.dirname(src)) for f in os.listdir(d) if f.endswith(".h")]
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+_sims = {}
+
+
+def sim_lib(name, *, pthread):
+    """The loaded library of tests/hostsim/<name>.cpp (a simulator on tests/hostsim/simshim.h), rebuilt first where it is stale.
+    pthread: the simulator runs its lanes as OS threads (LRA_SIM_THREADS)."""
+    if name not in _sims:
+        src, so = os.path.join(HERE, "hostsim", name + ".cpp"), os.path.join(HERE, "hostsim", f"_{name}.so")
+        if _stale(so, src):
+            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared"] + (["-pthread"] if pthread else []) + ["-DLRA_POSTSIM", src, "-o", so])
+        _sims[name] = ctypes.CDLL(so)
+    return _sims[name]
 
 
 def build():
@@ -149,24 +164,21 @@ def istft(D, n_fft, hop, win, wss, out_len, n_used, center=True, strip_groups=4,
 
 
 # ---- PCEN / band max-filter kernels (librosa_amd/csrc/lra_pcen.h) on host threads: tests/hostsim/postsim.cpp -----------------------
-POST_SRC = os.path.join(HERE, "hostsim", "postsim.cpp")
-POST_SO = os.path.join(HERE, "hostsim", "_postsim.so")
 _post = None
 
 
 def post_lib():
     global _post
     if _post is None:
-        deps = [POST_SRC] + [os.path.join(CSRC, h) for h in ("lra_pcen.h", "lra_cqt.h", "lra_hpss.h", "lra_mixed.h", "lra_rng.h")]
-        if not os.path.exists(POST_SO) or any(os.path.getmtime(d) > os.path.getmtime(POST_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", POST_SRC, "-o", POST_SO])
-        _post = ctypes.CDLL(POST_SO)
+        _post = sim_lib("postsim", pthread=True)
         c = ctypes
         _post.postsim_pcen.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_longlong, c.c_longlong, c.c_int] + [c.c_double] * 5 + [c.c_void_p, c.c_double, c.c_void_p]
         _post.postsim_maxfilter.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_int, c.c_longlong, c.c_int, c.c_int]
         _post.postsim_fir_decimate.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_longlong, c.c_longlong, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_int]
         _post.postsim_resample_poly.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_longlong, c.c_longlong, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_int]
         _post.postsim_fir_route.argtypes = [c.c_longlong, c.c_int, c.c_int, c.c_int]
+        _post.postsim_fir_plan.argtypes = [c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_void_p]
+        _post.postsim_fir_plan.restype = None
         _post.postsim_magnitude.argtypes = [c.c_void_p, c.c_void_p, c.c_longlong, c.c_int]
         _post.postsim_magphase.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_longlong, c.c_double, c.c_int]
         _post.postsim_hpss.argtypes = [c.c_void_p] * 4 + [c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_double, c.c_int, c.c_int]
@@ -233,8 +245,15 @@ def fir_decimate(x, taps, down, first, n_out, div=1.0, mul=1.0):
 
 
 def fir_route(n_out, n_taps, down, is_f64):
-    """The kernel the simulator's fir_decimate runs for these sizes: "halve4" | "opt4" | "opt1" | "direct" (postsim.cpp's copy of lra_fir_decimate_exec's selection)."""
+    """The kernel lra_fir_decimate_exec launches and the simulator's fir_decimate runs for these sizes: "halve4" | "opt4" | "opt1" | "direct" (lra_cqt.h: fir_plan)."""
     return ("halve4", "opt4", "opt1", "direct")[post_lib().postsim_fir_route(int(n_out), int(n_taps), int(down), int(bool(is_f64)))]
+
+
+def fir_plan(n_out, n_taps, down, is_f64):
+    """The whole of lra_cqt.h's fir_plan for these sizes: dict(route, opt, blocks_per_clip, lds_bytes)."""
+    out = np.zeros(4, np.int64)
+    post_lib().postsim_fir_plan(int(n_out), int(n_taps), int(down), int(bool(is_f64)), _p(out))
+    return dict(route=("halve4", "opt4", "opt1", "direct")[out[0]], opt=int(out[1]), blocks_per_clip=int(out[2]), lds_bytes=int(out[3]))
 
 
 def resample_poly(x, taps, up, down, first, n_out, div=1.0, mul=1.0):

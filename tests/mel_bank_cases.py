@@ -20,7 +20,7 @@ MELR_PMAX = 16      # csrc/lra_kernels.h
 MEL2_PMAX = 15      # csrc/lra_mel.h, build_mel_pieces
 PC_PMAX = 4         # csrc/lra_kernels_pc.h, pc_bank_ok
 PC_BANDS = 128
-MIXED_SIZES = (400, 1764, 240, 1000)  # csrc/lra_mixed_launch.h; with the ctx option "mixed" at 0 they take the rocFFT path
+MIXED_SIZES = (400, 1764, 240, 1000)  # csrc/lra_mixed_sizes.h; with the ctx option "mixed" at 0 they take the rocFFT path
 SIM_MIXED_SIZES = (400, 240, 1000)    # ... of which the simulator instantiates these (tests/hostsim/postsim.cpp)
 # float32 (n_fft, hops of the table) whose run-ordered form runs on the second-generation core (lra_kernels2.h: v2_cfg_ok, v2_hop_divisor)
 V2_HOPS = {2048: (512, 256), 1024: (256,)}

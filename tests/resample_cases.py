@@ -2,8 +2,8 @@
 general rational resampler of ``lra_resample_poly_exec``, against ``scipy.signal.upfirdn`` -- the plain C loop whose summation order the kernels of
 librosa_amd/csrc/lra_cqt.h promise to reproduce bit for bit.  Every input is seeded and every expectation is computed: there is no fixture file.
 
-``route()`` restates the selection of ``lra_fir_decimate_exec``; it is the third copy of it (the second is ``fir_route`` of tests/hostsim/postsim.cpp, which
-the host test compares with this one)."""
+``route()`` restates the selection of ``lra_fir_decimate_exec``; it is the second copy of it (the first is ``fir_plan`` of librosa_amd/csrc/lra_cqt.h, which
+the library launches from and the host simulator runs; the host test compares that one with this one)."""
 import numpy as np
 import scipy.signal
 

@@ -10,7 +10,7 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rhythm_edges.npz")
 
-# ---- the tempogram kernel's geometry, restated from librosa_amd/csrc/lra_rhythm.h and lra_mixed_launch.h ------------------------------------
+# ---- the tempogram kernel's geometry, restated from librosa_amd/csrc/lra_rhythm.h and lra_mixed_sizes.h ------------------------------------
 SIZES = (160, 200, 240, 320, 400, 480, 600, 640, 720, 800, 882, 960, 1000, 1200, 1280, 1440, 1600, 1764, 1920, 2000, 2400, 2646, 3200, 3528, 4800)
 WRITE, SUM, ARGMAX = 0, 1, 2
 GROUP, RED, LDS_MAX = 16, 64, 160 * 1024

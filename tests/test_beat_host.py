@@ -1,19 +1,13 @@
 """beat_track without a GPU: argument checks before any device work, the converters against tests/golden/beat.npz, and the kernel bodies of
 librosa_amd/csrc/lra_beat.h run on host threads (tests/hostsim/beatsim.cpp) on the reference's envelopes with the reference's BPM."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import beat_signals as BS
+import hostsim_util
 import librosa_amd as L
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "beatsim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_beatsim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -118,10 +112,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC, os.path.join(CSRC, "lra_beat.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("beatsim", pthread=True)
         c = ctypes
         _sim.beatsim_exec.argtypes = [c.c_void_p, c.c_longlong, c.c_longlong, c.c_int, c.c_void_p, c.c_int, c.c_double, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
                                       c.c_void_p, c.POINTER(c.c_int)]

@@ -2,13 +2,12 @@
 documented "not provided" errors before any device work, and the kernel bodies of librosa_amd/csrc/lra_chroma.h run on the host
 (tests/hostsim/chromasim.cpp) in both forms against every fixture case, under the bound of tests/chroma_cases.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import chroma_cases as CC
+import hostsim_util
 import librosa_amd as L
 import stft_oracle as O
 from librosa_amd import filters
@@ -16,10 +15,6 @@ from librosa_amd.feature import chroma as chroma_mod
 
 chroma_stft, chroma_cqt = L.feature.chroma_stft, L.feature.chroma_cqt
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "chromasim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_chromasim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 CODES = {None: 0, 1: 1, 2: 2, CC.INF: 3}
 
 
@@ -132,10 +127,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC, os.path.join(CSRC, "lra_chroma.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("chromasim", pthread=False)
         c = ctypes
         _sim.chromasim_exec.argtypes = [c.c_void_p] + [c.c_longlong] * 6 + [c.c_int, c.c_void_p, c.c_longlong, c.c_int, c.c_double, c.c_int, c.c_void_p, c.POINTER(c.c_int)]
     return _sim

@@ -3,19 +3,16 @@ librosa_amd/csrc/lra_onset.h run on host threads (tests/hostsim/onsetsim.cpp) ag
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostsim_util
 import librosa_amd as L
 from librosa_amd import onset as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "onset.npz")
-SIM_SRC = os.path.join(HERE, "hostsim", "onsetsim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_onsetsim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 
 CASE_NAMES = ["default", "lag2_max3", "hop441", "mixed400", "median_channels", "max_slices", "agg_false", "sum", "min", "detrend", "nocenter", "f64", "median_f64_max3", "S_given_ref",
               "S_lag_ge_frames", "S_lag_ge_frames_nocenter", "S_channels_odd", "S_nan_mean", "S_nan_median", "S_nan_max", "S_nan_false", "p75", "feature_amp_mel"]
@@ -109,10 +106,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC] + [os.path.join(CSRC, h) for h in ("lra_onset.h", "lra_db.h", "lra_pcen.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("onsetsim", pthread=True)
         c = ctypes
         _sim.onsetsim_exec.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_longlong, c.c_int, c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int,
                                        c.c_int, c.c_longlong, c.c_longlong, c.c_int, c.c_double, c.c_double, c.c_void_p, c.c_int, c.c_void_p]

@@ -2,22 +2,16 @@
 model against tests/golden/peaks.npz, and the kernel bodies of librosa_amd/csrc/lra_peaks.h run on host threads
 (tests/hostsim/peaksim.cpp) against every fixture case."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostsim_util
 import librosa_amd as L
 import peak_cases as PC
 from librosa_amd.util import peaks as P
 
 onset_detect, onset_backtrack, peak_pick = L.onset.onset_detect, L.onset.onset_backtrack, L.util.peak_pick
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "peaksim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_peaksim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -180,10 +174,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC, os.path.join(CSRC, "lra_peaks.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("peaksim", pthread=True)
         c = ctypes
         _sim.peaksim_pick.argtypes = [c.c_void_p, c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_longlong, c.c_longlong, c.c_longlong, c.c_longlong, c.c_double, c.c_longlong, c.c_int,
                                       c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_int)]

@@ -4,21 +4,16 @@ on every fixture case under the bounds of tests/pitch_cases.py: both layouts of 
 one, the radix select against np.median, and the histogram against np.histogram."""
 import ctypes
 import json
-import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+import hostsim_util
 import librosa_amd as L
 import pitch_cases as PC
 from librosa_amd.core import pitch as pitch_mod
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "pitchsim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_pitchsim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 REF_MAX, REF_ROW, REF_SCALAR = 0, 1, 2
 
 
@@ -138,10 +133,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC, os.path.join(CSRC, "lra_pitch.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("pitchsim", pthread=False)
         c = ctypes
         front = [c.c_void_p] + [c.c_longlong] * 6 + [c.c_int, c.c_longlong, c.c_longlong, c.c_int, c.c_double, c.c_void_p, c.c_double, c.c_double, c.c_longlong]
         _sim.pitchsim_piptrack.argtypes = front + [c.c_void_p, c.c_void_p] + [c.c_longlong] * 3

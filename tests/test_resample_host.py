@@ -1,7 +1,7 @@
 """The FIR decimator routes and the rational resampler without a GPU: that tests/resample_cases.py reaches every kernel of ``lra_fir_decimate_exec`` on either
 side of every limit of its selection, that the kernel bodies of librosa_amd/csrc/lra_cqt.h run on host threads (tests/hostsim/postsim.cpp) equal
-``scipy.signal.upfirdn`` bit for bit on every case, that the reference restatement is scipy's entry point, and that the simulator's copy of the selection is
-``resample_cases.route()``."""
+``scipy.signal.upfirdn`` bit for bit on every case, that the reference restatement is scipy's entry point, and that the library's own selection (``fir_plan`` of lra_cqt.h, which the simulator runs
+and exports) is ``resample_cases.route()``."""
 import numpy as np
 import pytest
 import scipy.signal
@@ -140,7 +140,21 @@ def test_reference_is_scipy_resample_poly(case):
         assert np.array_equal(c["want"], CQ.resample(c["x"], orig_sr=c["down"], target_sr=1, res_type="polyphase", scale=True))
 
 
-# ---- the simulator's copy of the selection --------------------------------------------------------------------------------------------------
+# ---- the library's own selection (lra_cqt.h: fir_plan, what lra_fir_decimate_exec launches and the simulator runs) against route() ------------
+def test_plan_geometry_is_what_the_route_implies():
+    """blocks_per_clip and lds_bytes of every case, from route()'s arithmetic: 1024 outputs a workgroup on the four-output routes and 256 on the others; the padded
+    span of pairs for the halving kernel, the workgroup's input span for the strided ones, nothing for the direct one.  No staged route asks for more than 64 KiB."""
+    for case in RC.CASES:
+        c = built(case)
+        elem, n_taps, down, n_out = c["x"].dtype.itemsize, len(c["taps"]), c["down"], c["n_out"]
+        plan = H.fir_plan(n_out, n_taps, down, elem == 8)
+        opt = 4 if c["route"] in ("halve4", "opt4") else 1
+        span2 = 2046 + n_taps
+        lds = {"halve4": (span2 + span2 // 8 + 1) * 2 * elem, "opt4": (1023 * down + n_taps) * elem, "opt1": (255 * down + n_taps) * elem, "direct": 0}[c["route"]]
+        assert plan == dict(route=c["route"], opt=opt, blocks_per_clip=-(-n_out // (256 * opt)), lds_bytes=lds), RC.case_id(case)
+        assert plan["lds_bytes"] <= 64 * 1024 and (plan["lds_bytes"] > 0) == (c["route"] != "direct"), RC.case_id(case)
+
+
 def test_simulator_routes_like_route():
     for case in RC.CASES:
         c = built(case)

@@ -1,20 +1,14 @@
 """tempogram / tempo without a GPU: argument checks before any device work, the host tables against tests/golden/rhythm.npz, and the kernel
 bodies of librosa_amd/csrc/lra_rhythm.h run on host threads (tests/hostsim/rhythmsim.cpp) on the reference's envelopes."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostsim_util
 import librosa_amd as L
 import rhythm_cases as RC
 from librosa_amd.feature import rhythm as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "rhythmsim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_rhythmsim.so")
-CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -95,10 +89,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC] + [os.path.join(CSRC, h) for h in ("lra_rhythm.h", "lra_mixed.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("rhythmsim", pthread=True)
         c = ctypes
         _sim.rhythmsim_exec.argtypes = [c.c_void_p, c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
                                         c.c_int, c.POINTER(c.c_int)]
@@ -122,6 +113,22 @@ def sim_exec(env, W, center, window, norm, mode, logprior=None, bpms=None, direc
     rc = sim_lib().rhythmsim_exec(_p(env), batch, n, int(env.dtype == np.float64), W, int(center), _p(win), norm, mode, _p(logprior), _p(bpms), _p(out), int(direct), ctypes.byref(flag))
     assert rc == 0
     return out.reshape(lead + shape[1:]), bool(flag.value)
+
+
+def test_transform_lengths_are_the_restated_ones():
+    """The library's own choice of transform (lra_rhythm.h: prepare, through the simulator) against tests/rhythm_edges.py's restatement: at, one below
+    and one above the largest window of every size, where the choice changes; and the tile and the LDS total that go with it."""
+    import rhythm_edges as E
+
+    sim_lib().rhythmsim_geometry.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    for N in E.SIZES:
+        for W in ((N + 1) // 2 - 1, (N + 1) // 2, (N + 1) // 2 + 1):
+            for mode in (R._WRITE, R._SUM, R._ARGMAX):
+                out = np.zeros(3, np.int32)
+                sim_lib().rhythmsim_geometry(W, mode, _p(out))
+                tile = mode == R._WRITE and E.lds_total(W, mode, True) <= E.LDS_MAX
+                assert (int(out[0]), bool(out[1]), int(out[2])) == (E.transform_length(W), tile, E.lds_total(W, mode, tile)), (N, W, mode)
+    assert E.transform_length((E.SIZES[-1] + 1) // 2 + 1) == 0  # the sweep ends on the direct kernel
 
 
 def _envelope_case(z, cases, inputs, name):

@@ -6,19 +6,17 @@ Measured through the simulator (settled frames): f0 within 1.6e-15 relative of t
 live frames is unsettled."""
 import ctypes
 import os
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 
+import hostsim_util
 import librosa_amd as L
 import yin_cases as YC
 from librosa_amd.core import pitch as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIM_SRC = os.path.join(HERE, "hostsim", "yinsim.cpp")
-SIM_SO = os.path.join(HERE, "hostsim", "_yinsim.so")
 CSRC = os.path.join(os.path.dirname(HERE), "librosa_amd", "csrc")
 PAD_MODES = {"constant": 0, "reflect": 1, "edge": 2, "symmetric": 3}
 
@@ -136,10 +134,7 @@ _sim = None
 def sim_lib():
     global _sim
     if _sim is None:
-        deps = [SIM_SRC] + [os.path.join(CSRC, h) for h in ("lra_yin.h", "lra_mixed.h")]
-        if not os.path.exists(SIM_SO) or any(os.path.getmtime(d) > os.path.getmtime(SIM_SO) for d in deps):
-            subprocess.check_call(["g++", "-O1", "-std=c++17", "-w", "-fPIC", "-shared", "-pthread", "-DLRA_POSTSIM", SIM_SRC, "-o", SIM_SO])
-        _sim = ctypes.CDLL(SIM_SO)
+        _sim = hostsim_util.sim_lib("yinsim", pthread=True)
         c = ctypes
         _sim.yinsim_exec.argtypes = [c.c_void_p, c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, c.c_int, c.c_void_p,
                                      c.c_void_p, c.c_void_p, c.c_int]
@@ -203,18 +198,19 @@ def test_case_geometry_matches_the_kernels_constants():
 
 
 def test_size_lists_are_the_librarys():
-    """The simulator and tests/yin_cases.py carry copies of LRA_MIXED_SIZES: both must be csrc/lra_mixed_launch.h's list, and the simulator's
-    choice of transform must be the library's own (lra_yin_lds_bytes: host arithmetic on the library's list, no device)."""
+    """tests/yin_cases.py carries a copy of LRA_MIXED_SIZES: it must be csrc/lra_mixed_sizes.h's list, which the simulators include and nothing
+    repeats; and the simulator's choice of transform must be the library's own (lra_yin_lds_bytes: host arithmetic on the library's list, no device)."""
+    import glob
     import re
 
     from librosa_amd import _native
 
-    text = open(os.path.join(CSRC, "lra_mixed_launch.h")).read()
+    text = open(os.path.join(CSRC, "lra_mixed_sizes.h")).read()
     line = re.search(r"#define LRA_MIXED_SIZES\(X\)(.*)", text).group(1)
     sizes = tuple(int(v) for v in re.findall(r"X\((\d+)\)", line))
     assert sizes == YC.SIZES and len(sizes) >= 25
-    sim_line = re.search(r"#define LRA_MIXED_SIZES\(X\)(.*)", open(SIM_SRC).read()).group(1)
-    assert tuple(int(v) for v in re.findall(r"X\((\d+)\)", sim_line)) == sizes
+    sources = glob.glob(os.path.join(CSRC, "*")) + glob.glob(os.path.join(HERE, "hostsim", "*.cpp")) + glob.glob(os.path.join(HERE, "hostsim", "*.h"))
+    assert sum(open(f, errors="replace").read().count("#define LRA_MIXED_SIZES") for f in sources if os.path.isfile(f)) == 1
     lib = _native.load_library()
     for N in sizes + (4801,):  # at, one below and one above every size: where the choice changes
         for total in (N - 1, N, N + 1):

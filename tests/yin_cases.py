@@ -34,7 +34,7 @@ SR = 22050
 FRAME_RUN = 16                # frames per workgroup (csrc/lra_yin.h: kYinGroup)
 EPS_FACTOR, F0_FACTOR, F0_FLOOR_ULP = 4.0, 16.0, 4.0
 MAX_UNSETTLED_CASE, MAX_UNSETTLED_ALL = 0.10, 0.03
-# the transform lengths the device library is compiled for (csrc/lra_mixed_launch.h: LRA_MIXED_SIZES)
+# the transform lengths the device library is compiled for (csrc/lra_mixed_sizes.h: LRA_MIXED_SIZES)
 SIZES = (160, 200, 240, 320, 400, 480, 600, 640, 720, 800, 882, 960, 1000, 1200, 1280, 1440, 1600, 1764, 1920, 2000, 2400, 2646, 3200, 3528, 4800)
 
 
