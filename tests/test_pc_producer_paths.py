@@ -76,6 +76,15 @@ _GPU_CASES += [(1293, 512, 2.0, "hann", "constant", "config"), (1293, 512, 2.0, 
                (12, 256, 1.0, "hann", "reflect", "config")]
 
 
+def _sim_iters(n_frames, hop, power, window, pad_mode, kind):
+    """The producer-slot lengths at which the simulator half runs this device case."""
+    if pad_mode != "constant":
+        return []
+    if kind == "lane0":
+        return [3] if n_frames == 5 else []
+    return sorted({it for nf, it, h, p in _SIM_CASES if (nf, h, p) == (n_frames, hop, power)}) if window == "hann" else []
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_frames,hop,power,window,pad_mode,kind", _GPU_CASES)
 def test_gpu_producer_paths(n_frames, hop, power, window, pad_mode, kind):
@@ -104,5 +113,19 @@ def test_gpu_producer_paths(n_frames, hop, power, window, pad_mode, kind):
         for i in range(3):
             Mi = L.feature.melspectrogram(y=yt[i], **kw).cpu().numpy()
             assert np.array_equal(Mi, outs[1][i]), i
+        # once more at the simulator cases' own producer-slot lengths for this clip (test_sim_producer_slot_edges, test_sim_lane0_pairing)
+        for iters in _sim_iters(n_frames, hop, power, window, pad_mode, kind):
+            ctx.set_option("stft_iters", iters)
+            forced = []
+            for pc in (0, 1):
+                ctx.set_option("mel_pc", pc)
+                M = L.feature.melspectrogram(y=yt, **kw).cpu().numpy()
+                assert M.shape == ref.shape and not np.isnan(M).any()
+                rel = float(np.max(np.abs(M - ref) / np.abs(ref)))
+                print(f"stft_iters {iters} mel_pc {pc}: max rel err against the oracle {rel:.3g}")
+                assert np.all(np.abs(M - ref) <= 1e-4 * np.abs(ref)), (iters, pc, rel)
+                forced.append(M)
+            assert np.all(np.abs(forced[1] - forced[0]) <= 2e-5 * np.abs(forced[0])), iters
     finally:
         ctx.set_option("mel_pc", 1)  # (the library's default)
+        ctx.set_option("stft_iters", 0)

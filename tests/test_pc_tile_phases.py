@@ -14,6 +14,9 @@ import stft_oracle as O
 _SIM_CASES = [(16 + k, it, nm) for k, it, nm in zip(range(8), (3, 5, 9, 10, 11, 6, 13, 7), (128, 125, 120, 128, 125, 120, 128, 128))]
 
 
+_SIM_ITERS = {nf: it for nf, it, _ in _SIM_CASES}
+
+
 def _check_diag(d):
     assert d["races"] == 0 and d["uninit"] == 0, d
 
@@ -58,8 +61,20 @@ def test_gpu_consumer_tile_phases(n_frames, n_mels):
         for i in range(3):
             Mi = L.feature.melspectrogram(y=yt[i], sr=22050, n_fft=2048, hop_length=512, n_mels=n_mels).cpu().numpy()
             assert np.array_equal(Mi, outs[1][i]), i
+        # once more at the simulator case's own producer-slot length (the auto rule gives these short clips slots of at most four frames)
+        if n_frames in _SIM_ITERS:
+            ctx.set_option("stft_iters", _SIM_ITERS[n_frames])
+            forced = []
+            for pc in (0, 1):
+                ctx.set_option("mel_pc", pc)
+                M = L.feature.melspectrogram(y=yt, sr=22050, n_fft=2048, hop_length=512, n_mels=n_mels).cpu().numpy()
+                assert M.shape == ref.shape and not np.isnan(M).any()
+                assert np.all(np.abs(M - ref) <= 1e-4 * np.abs(ref)), (pc, _SIM_ITERS[n_frames], float(np.max(np.abs(M - ref) / np.abs(ref))))
+                forced.append(M)
+            assert np.all(np.abs(forced[1] - forced[0]) <= 2e-5 * np.abs(forced[0]))
     finally:
         ctx.set_option("mel_pc", 1)  # (the library's default)
+        ctx.set_option("stft_iters", 0)
 
 
 @pytest.mark.gpu
