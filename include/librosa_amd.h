@@ -425,6 +425,37 @@ int64_t lra_yin_lds_bytes(int frame_length, int max_period);
 int lra_yin_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, int dtype, int frame_length, int hop_length, int center, int pad_mode, int min_period, int max_period,
                  double trough_threshold, double sr, int mode, void* f0, void* frames, void* shifts);
 
+/* ---- sequence.viterbi, viterbi_discriminative, viterbi_binary: librosa/sequence.py:1174-1259 (_viterbi), 1280-1432, 1455-1679, 1702-1874 --- */
+#define LRA_VITERBI_GENERATIVE 0      /* log_prob = log(prob + eps)                                   (:1395) */
+#define LRA_VITERBI_DISCRIMINATIVE 1  /* log_prob = log(prob + eps) - log_marginal[state]             (:1653) */
+#define LRA_VITERBI_BINARY 2          /* prob [chain][step]; the rows 1 - p and p of a 2-state chain, minus log_marginal[chain % n_labels][row] (:1853-1854) */
+#define LRA_VITERBI_LOG 3             /* prob is a float64 log table already: the transpose alone */
+#define LRA_VITERBI_FLAG_NEGATIVE 1   /* some prob < 0 */
+#define LRA_VITERBI_FLAG_ABOVE_ONE 2  /* some prob > 1 */
+#define LRA_VITERBI_FLAG_COLUMN_SUM 4 /* DISCRIMINATIVE: some column's sum over the states is not np.allclose to 1 */
+#define LRA_VITERBI_LDS_MAX (160 * 1024)
+#define LRA_VITERBI_MAX_STATES 8192
+/* Bytes of LDS a decode workgroup needs for n_states and the longest predecessor list n_pred (0: full search); host arithmetic only.  Two
+ * float64 value rows (16 n_states bytes) and the argmax scratch, plus log_trans where a full search's table fits beside them; up to
+ * LRA_VITERBI_SMALL_MAX states, a table per chain of the workgroup.  Above LRA_VITERBI_MAX_STATES the answer exceeds LRA_VITERBI_LDS_MAX
+ * and lra_viterbi_exec refuses (LRA_EINVAL). */
+int64_t lra_viterbi_lds_bytes(int n_states, int n_pred);
+/* prob: [chains][n_states][n_steps] of `dtype` (device; BINARY: [chains][n_steps], n_states = 2), never written -> log_prob: float64
+ * [chains][n_steps][n_states].  The logarithm is taken in `dtype` after adding eps (util.tiny of prob's type) and widened exactly; BINARY takes
+ * 1 - p in `dtype` and both logarithms in float64.  log_marginal: float64 [n_states] (DISCRIMINATIVE) or [n_labels][2] (BINARY), else NULL.
+ * work: 4 bytes (device).  *flags: the LRA_VITERBI_FLAG_* bits met (this waits for the stream); the caller raises before it decodes. */
+int lra_viterbi_prep_exec(lra_ctx* ctx, const void* prob, int dtype, int kind, int64_t chains, int n_states, int64_t n_steps, double eps, const void* log_marginal, int n_labels,
+                          void* log_prob, void* work, int* flags);
+/* _viterbi (:1174-1259) of every chain: value[0] = log_prob[0] + log_p_init; value[t][j] = log_prob[t][j] + max_k (value[t - 1][k] + log_trans[k][j]),
+ * the first k on a tie and 0 where every candidate is -inf; the last state np.argmax(value[-1]); the pointers walked back.  Chain c reads table
+ * c % n_tables of log_trans [n_tables][n_states][n_states] and log_p_init [n_tables][n_states] (float64, device); n_tables > 1 only up to
+ * LRA_VITERBI_SMALL_MAX states.  threshold: -inf for the full search; otherwise only k with log_trans[k][j] >= threshold are candidates, and above
+ * LRA_VITERBI_SMALL_MAX states they come as lists, ascending in k: pred_k uint16 [n_pred][n_states], pred_lt float64 [n_pred][n_states], pred_n int32
+ * [n_states] (device).  ptr: uint16 scratch [chains][n_steps][n_states].  states: uint16 [chains][n_steps]; logp: float64 [chains]. */
+#define LRA_VITERBI_SMALL_MAX 32
+int lra_viterbi_exec(lra_ctx* ctx, const void* log_prob, int64_t chains, int n_states, int64_t n_steps, const void* log_trans, const void* log_p_init, int n_tables, double threshold,
+                     int n_pred, const void* pred_k, const void* pred_lt, const void* pred_n, void* ptr, void* states, void* logp);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

@@ -117,6 +117,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int64, c_int64, c_int64]),
     "lra_yin_lds_bytes": (c_int64, [c_int, c_int]),
     "lra_yin_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "lra_viterbi_lds_bytes": (c_int64, [c_int, c_int]),
+    "lra_viterbi_prep_exec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_double, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "lra_viterbi_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -646,6 +649,24 @@ class Context:
         _check(self.lib.lra_yin_exec(self.handle, c_void_p(y_ptr), int(batch), int(n), dtype_code(dtype), int(frame_length), int(hop_length), int(bool(center)),
                                      {"constant": 0, "reflect": 1, "edge": 2, "symmetric": 3}[pad_mode], int(min_period), int(max_period), float(trough_threshold), float(sr), int(mode),
                                      c_void_p(f0_ptr or None), c_void_p(frames_ptr or None), c_void_p(shifts_ptr or None)))
+
+    VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
+    VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits
+
+    def viterbi_prep_exec(self, prob_ptr, dtype, kind, chains, n_states, n_steps, eps, log_marginal_ptr, n_labels, log_prob_ptr, work_ptr):
+        """prob -> the float64 log table [chain][step][state] (``include/librosa_amd.h``: lra_viterbi_prep_exec).  Returns the range flags met
+        (this waits for the stream)."""
+        flags = c_int(0)
+        _check(self.lib.lra_viterbi_prep_exec(self.handle, c_void_p(prob_ptr), dtype_code(dtype), int(kind), int(chains), int(n_states), int(n_steps), float(eps),
+                                              c_void_p(log_marginal_ptr or None), int(n_labels), c_void_p(log_prob_ptr), c_void_p(work_ptr), byref(flags)))
+        return int(flags.value)
+
+    def viterbi_exec(self, log_prob_ptr, chains, n_states, n_steps, log_trans_ptr, log_p_init_ptr, n_tables, threshold, n_pred, pred_k_ptr, pred_lt_ptr, pred_n_ptr, ptr_ptr, states_ptr,
+                     logp_ptr):
+        """The decode of every chain (``include/librosa_amd.h``: lra_viterbi_exec)."""
+        _check(self.lib.lra_viterbi_exec(self.handle, c_void_p(log_prob_ptr), int(chains), int(n_states), int(n_steps), c_void_p(log_trans_ptr or None), c_void_p(log_p_init_ptr),
+                                         int(n_tables), float(threshold), int(n_pred), c_void_p(pred_k_ptr or None), c_void_p(pred_lt_ptr or None), c_void_p(pred_n_ptr or None),
+                                         c_void_p(ptr_ptr), c_void_p(states_ptr), c_void_p(logp_ptr)))
 
     PITCH_REF_MAX, PITCH_REF_ROW, PITCH_REF_SCALAR = 0, 1, 2   # the LRA_PITCH_REF_* values
 
