@@ -10,6 +10,7 @@
 #include "../../librosa_amd/csrc/lra_cqt.h"
 #include "../../librosa_amd/csrc/lra_hpss.h"
 #include "../../librosa_amd/csrc/lra_mixed.h"
+#include "../../librosa_amd/csrc/lra_mixed_sizes.h"
 #include "../../librosa_amd/csrc/lra_rng.h"
 
 namespace {
@@ -341,14 +342,31 @@ template <class T, int N> int sim_cqt_octave(lra::mixed::CqtArgs<T> a, long long
     return 0;
 }
 template <class T> int sim_cqt_octave_n(int n_fft, const lra::mixed::CqtArgs<T>& a, long long batch) {
+    switch (n_fft) {  // every frame length of the library's list (lra_mixed_sizes.h)
+#define SIM_CQT_CASE(N) \
+    case N: return sim_cqt_octave<T, N>(a, batch);
+        LRA_CQT_SIZES(SIM_CQT_CASE)
+#undef SIM_CQT_CASE
+        default: return 1;
+    }
+}
+// the launch of cqt_octaves_merged (lra_api.hip): mixed_cqt_multi_kernel over octaves that share the frame length and the frame grid
+template <class T, int N> int sim_cqt_multi(lra::mixed::CqtMultiArgs<T> m, long long batch) {
+    using namespace lra::mixed;
+    static_assert(cqt_lds_bytes<T, N>() <= (int)sizeof(g_postsim_dyn_lds), "simulated LDS too small");
+    constexpr int F = cqt_frames_per_group<T, N>();
+    const int groups = (m.oct[0].n_frames + F - 1) / F;
+    for (int i = 0; i < m.n_oct; ++i) m.oct[i].groups_per_clip = groups;
+    m.blocks_per_octave = (unsigned)(batch * groups);
+    run_grid(m.blocks_per_octave * (unsigned)m.n_oct, NT, [=] { mixed_cqt_multi_kernel<T, N>(m); });
+    return 0;
+}
+template <class T> int sim_cqt_multi_n(int n_fft, const lra::mixed::CqtMultiArgs<T>& m, long long batch) {
     switch (n_fft) {
-        case 32: return sim_cqt_octave<T, 32>(a, batch);
-        case 64: return sim_cqt_octave<T, 64>(a, batch);
-        case 128: return sim_cqt_octave<T, 128>(a, batch);
-        case 256: return sim_cqt_octave<T, 256>(a, batch);
-        case 512: return sim_cqt_octave<T, 512>(a, batch);
-        case 1024: return sim_cqt_octave<T, 1024>(a, batch);
-        case 2048: return sim_cqt_octave<T, 2048>(a, batch);
+#define SIM_CQT_CASE(N) \
+    case N: return sim_cqt_multi<T, N>(m, batch);
+        LRA_CQT_SIZES(SIM_CQT_CASE)
+#undef SIM_CQT_CASE
         default: return 1;
     }
 }
@@ -375,3 +393,72 @@ extern "C" int postsim_cqt_octave(int n_fft, int is_f64, const void* y, long lon
     return sim_cqt_octave_n<float>(n_fft, a, batch);
 }
 
+// one octave of a merged launch, as lra_cqt_octave (include/librosa_amd.h) describes it plus its own signal
+struct postsim_cqt_oct {
+    const void* y;
+    long long n, y_stride;
+    int hop, bin0, row0, n_rows;
+    const int* row_ptr;
+    const int* col;
+    const void* val;
+};
+
+// the launch of cqt_octaves_merged (lra_api.hip): sqrt_len is the whole transform's table, each octave reads it from its bin0 on
+extern "C" int postsim_cqt_octaves_merged(int n_fft, int is_f64, const postsim_cqt_oct* octs, int n_oct, long long batch, int pad_mode, const void* tw_m, const void* tw_n,
+                                          const double* sqrt_len, void* out, long long n_frames, int n_total) {
+    if (n_oct < 1 || n_oct > lra::mixed::kCqtMaxMerged) return 2;
+    auto fill = [&](auto& m, auto tag) {
+        using T = decltype(tag);
+        m.n_oct = 0;
+        for (int i = 0; i < n_oct; ++i) {
+            const postsim_cqt_oct& o = octs[i];
+            if (o.n_rows == 0) continue;  // (as there: an octave without rows takes no blocks)
+            auto& a = m.oct[m.n_oct++];
+            a.y = (const T*)o.y; a.y_stride = o.y_stride; a.n = o.n; a.hop = o.hop; a.pad = n_fft / 2; a.pad_mode = pad_mode;
+            a.tw_m = (const lra::mixed::cpx<T>*)tw_m; a.tw_n = (const lra::mixed::cpx<T>*)tw_n;
+            a.row_ptr = o.row_ptr; a.col = o.col; a.val = (const lra::mixed::cpx<T>*)o.val; a.sqrt_len = sqrt_len ? sqrt_len + o.bin0 : nullptr;
+            a.out = (lra::mixed::cpx<T>*)out; a.n_frames = (int)n_frames; a.n_total = n_total; a.bin0 = o.bin0; a.row0 = o.row0; a.n_rows = o.n_rows;
+            a.nonfinite_flag = nullptr;
+        }
+    };
+    if (is_f64) {
+        lra::mixed::CqtMultiArgs<double> m = lra::mixed::CqtMultiArgs<double>();
+        fill(m, double());
+        return m.n_oct ? sim_cqt_multi_n<double>(n_fft, m, batch) : 0;
+    }
+    lra::mixed::CqtMultiArgs<float> m = lra::mixed::CqtMultiArgs<float>();
+    fill(m, float());
+    return m.n_oct ? sim_cqt_multi_n<float>(n_fft, m, batch) : 0;
+}
+
+// the library's own list of octave frame lengths (LRA_CQT_SIZES): writes up to `cap` of them, returns how many there are
+extern "C" int postsim_cqt_sizes(int* out, int cap) {
+    int n = 0;
+#define SIM_CQT_CASE(N) \
+    if (n < cap) out[n] = N; \
+    ++n;
+    LRA_CQT_SIZES(SIM_CQT_CASE)
+#undef SIM_CQT_CASE
+    return n;
+}
+extern "C" int postsim_cqt_octave_supported(int n_fft) { return lra::mixed::in_cqt_size_list(n_fft) ? 1 : 0; }
+
+// what cqt_frames_per_group_of (lra_mixed_inst.hip) answers, and the instance's dynamic LDS; 0 outside the list
+extern "C" int postsim_cqt_frames_per_group(int n_fft, int is_f64) {
+    switch (n_fft) {
+#define SIM_CQT_CASE(N) \
+    case N: return is_f64 ? lra::mixed::cqt_frames_per_group<double, N>() : lra::mixed::cqt_frames_per_group<float, N>();
+        LRA_CQT_SIZES(SIM_CQT_CASE)
+#undef SIM_CQT_CASE
+        default: return 0;
+    }
+}
+extern "C" int postsim_cqt_lds_bytes(int n_fft, int is_f64) {
+    switch (n_fft) {
+#define SIM_CQT_CASE(N) \
+    case N: return is_f64 ? lra::mixed::cqt_lds_bytes<double, N>() : lra::mixed::cqt_lds_bytes<float, N>();
+        LRA_CQT_SIZES(SIM_CQT_CASE)
+#undef SIM_CQT_CASE
+        default: return 0;
+    }
+}

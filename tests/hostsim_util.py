@@ -276,6 +276,71 @@ def cqt_project(D, csr, n_frames, n_total, bin0, row0, n_rows, sqrt_len=None):
     return out
 
 
+def cqt_sizes():
+    """The fused octave kernel's frame lengths: the library's own list (csrc/lra_mixed_sizes.h, LRA_CQT_SIZES), as the simulator was compiled with it."""
+    buf = np.zeros(64, np.int32)
+    count = post_lib().postsim_cqt_sizes(_p(buf), len(buf))
+    assert 0 < count <= len(buf)
+    return tuple(int(v) for v in buf[:count])
+
+
+def cqt_octave_supported(n_fft):
+    """lra_cqt_octave_supported (lra_api.hip): the same list function."""
+    return bool(post_lib().postsim_cqt_octave_supported(int(n_fft)))
+
+
+def cqt_frames_per_group(n_fft, dtype):
+    """Frames per workgroup of the (n_fft, dtype) instance: what cqt_frames_per_group_of answers in the library."""
+    return int(post_lib().postsim_cqt_frames_per_group(int(n_fft), int(np.dtype(dtype).itemsize == 8)))
+
+
+def cqt_lds_bytes(n_fft, dtype):
+    """Dynamic LDS of the (n_fft, dtype) instance."""
+    return int(post_lib().postsim_cqt_lds_bytes(int(n_fft), int(np.dtype(dtype).itemsize == 8)))
+
+
+def _cqt_twiddles(n_fft, f64):
+    ct = np.complex128 if f64 else np.complex64
+    M = int(n_fft) // 2
+    tw_m = np.ascontiguousarray(np.exp(-2j * np.pi * np.arange(M, dtype=np.float64) / M).astype(ct))
+    tw_n = np.ascontiguousarray(np.exp(-2j * np.pi * np.arange(M + 1, dtype=np.float64) / n_fft).astype(ct))
+    return tw_m, tw_n
+
+
+def cqt_octave(y_ptr, batch, n, y_stride, n_fft, hop, pad_mode, row_ptr, col_ptr, val_ptr, sqrt_len_ptr, out_ptr, n_frames, n_total, bin0, row0, n_rows, dtype):
+    """mixed_cqt_kernel (csrc/lra_mixed.h) through the simulator, on host addresses: the arguments of librosa_amd._native.Context.cqt_octave_exec."""
+    c = ctypes
+    f64 = np.dtype(dtype) == np.float64
+    tw_m, tw_n = _cqt_twiddles(n_fft, f64)
+    fn = post_lib().postsim_cqt_octave
+    fn.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_longlong, c.c_longlong, c.c_longlong, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                   c.c_longlong, c.c_int, c.c_int, c.c_int, c.c_int]
+    rc = fn(int(n_fft), int(f64), y_ptr, batch, n, y_stride, int(hop), PAD_MODES[pad_mode], tw_m.ctypes.data, tw_n.ctypes.data, row_ptr, col_ptr, val_ptr, sqrt_len_ptr or None, out_ptr, n_frames,
+            int(n_total), int(bin0), int(row0), int(n_rows))
+    assert rc == 0, f"simulator: n_fft={n_fft} is not a frame length of the fused octave kernel"
+
+
+class _CqtOct(ctypes.Structure):
+    _fields_ = [("y", ctypes.c_void_p), ("n", ctypes.c_longlong), ("y_stride", ctypes.c_longlong), ("hop", ctypes.c_int), ("bin0", ctypes.c_int), ("row0", ctypes.c_int), ("n_rows", ctypes.c_int),
+                ("row_ptr", ctypes.c_void_p), ("col", ctypes.c_void_p), ("val", ctypes.c_void_p)]
+
+
+def cqt_octaves_merged(octaves, batch, n_fft, pad_mode, sqrt_len_ptr, out_ptr, n_frames, n_total, dtype):
+    """mixed_cqt_multi_kernel through the simulator, the launch of lra_api.hip's cqt_octaves_merged.  octaves: dicts of host addresses
+    (y, row_ptr, col, val) and n, y_stride, hop, bin0, row0, n_rows; sqrt_len_ptr: the whole result's table, read from each octave's bin0 on."""
+    c = ctypes
+    f64 = np.dtype(dtype) == np.float64
+    tw_m, tw_n = _cqt_twiddles(n_fft, f64)
+    arr = (_CqtOct * len(octaves))()
+    for slot, o in zip(arr, octaves):
+        for name, _ in _CqtOct._fields_:
+            setattr(slot, name, o[name])
+    fn = post_lib().postsim_cqt_octaves_merged
+    fn.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_int, c.c_longlong, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_longlong, c.c_int]
+    rc = fn(int(n_fft), int(f64), c.cast(arr, c.c_void_p), len(octaves), batch, PAD_MODES[pad_mode], tw_m.ctypes.data, tw_n.ctypes.data, sqrt_len_ptr or None, out_ptr, n_frames, int(n_total))
+    assert rc == 0, f"simulator: merged launch of {len(octaves)} octaves at n_fft={n_fft} not served (rc {rc})"
+
+
 def hpss(D, *, win_harm=31, win_perc=31, power=2.0, margin_harm=1.0, margin_perc=1.0, want_mask=False):
     """D: (batch, frames, bins) complex or real, the STFT kernel's layout -> (harmonic, percussive) through the kernel bodies of
     lra_magnitude_exec / lra_hpss_exec."""
