@@ -456,6 +456,24 @@ int lra_viterbi_prep_exec(lra_ctx* ctx, const void* prob, int dtype, int kind, i
 int lra_viterbi_exec(lra_ctx* ctx, const void* log_prob, int64_t chains, int n_states, int64_t n_steps, const void* log_trans, const void* log_p_init, int n_tables, double threshold,
                      int n_pred, const void* pred_k, const void* pred_lt, const void* pred_n, void* ptr, void* states, void* logp);
 
+/* ---- the back half of pyin around the decode: librosa.pyin, librosa/core/pitch.py:796-852 and __pyin_helper :855-931 ---------------------- */
+#define LRA_PYIN_LDS_MAX (160 * 1024)
+/* Bytes of LDS a workgroup of lra_pyin_obs_exec needs (host arithmetic only): per frame the voiced row (8 n_pitch_bins) and two counters per
+ * threshold (8 n_thresholds), four frames per workgroup, halved until they fit; above LRA_PYIN_LDS_MAX the call is refused (LRA_EINVAL). */
+int64_t lra_pyin_lds_bytes(int n_pitch_bins, int n_thresholds);
+/* cmnd, shifts: float64 [clips][n_lags][n_frames] (device; what lra_yin_exec writes in LRA_YIN_FRAMES mode for float64 samples), never written
+ * -> log_prob: float64 [clips][n_frames][2 n_pitch_bins], the layout lra_viterbi_exec reads, holding log(observation_probs + tiny) of
+ * __pyin_helper (:870-929); voiced_prob: float64 [clips][n_frames].  Host tables (float64, device): thresholds [n_thresholds] =
+ * np.linspace(0, 1, n_thresholds + 1)[1:]; beta_probs [n_thresholds]; beta_prefix [n_thresholds + 1] = np.sum(beta_probs[:m]); boltz_e
+ * [n_lags + 1] = exp(-lambda k); boltz_fact [n_lags + 1] = (1 - exp(-lambda)) / (1 - exp(-lambda N)) (scipy's boltzmann._pmf is
+ * boltz_fact[N] * boltz_e[k]).  A zero probability stores log_tiny as given. */
+int lra_pyin_obs_exec(lra_ctx* ctx, const void* cmnd, const void* shifts, int64_t clips, int n_lags, int64_t n_frames, const void* thresholds, const void* beta_probs,
+                      const void* beta_prefix, const void* boltz_e, const void* boltz_fact, int n_thresholds, double sr, double fmin, int min_period, int n_pitch_bins,
+                      int n_bins_per_semitone, double no_trough_prob, double tiny, double log_tiny, void* log_prob, void* voiced_prob);
+/* states: uint16 [n] (device) -> f0: float64 [n] = freqs[state % n_pitch_bins] (freqs: float64 [n_pitch_bins], device), voiced_flag: one byte per
+ * element, state < n_pitch_bins; fill != 0: f0 = fill_na where not voiced (:844-850). */
+int lra_pyin_finish_exec(lra_ctx* ctx, const void* states, int64_t n, int n_pitch_bins, const void* freqs, int fill, double fill_na, void* f0, void* voiced_flag);
+
 /* ---- constant-Q / variable-Q transform: librosa.cqt / librosa.vqt, librosa/core/constantq.py:42-225, 820-1122 ---------------------
  * The octave recursion (:1054-1099) is, per octave: lra_stft_exec with a rectangular window (__cqt_response, :1202-1204), then
  * lra_cqt_project_exec (the sparse filter basis applied to every frame, :1213-1218, with the length scaling :1116-1118 and the

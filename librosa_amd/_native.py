@@ -117,6 +117,10 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int64, c_int64, c_int64]),
     "lra_yin_lds_bytes": (c_int64, [c_int, c_int]),
     "lra_yin_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    "lra_pyin_lds_bytes": (c_int64, [c_int, c_int]),
+    "lra_pyin_obs_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_int, c_int, c_double,
+                                  c_double, c_double, c_void_p, c_void_p]),
+    "lra_pyin_finish_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p]),
     "lra_viterbi_lds_bytes": (c_int64, [c_int, c_int]),
     "lra_viterbi_prep_exec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_double, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_viterbi_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -649,6 +653,18 @@ class Context:
         _check(self.lib.lra_yin_exec(self.handle, c_void_p(y_ptr), int(batch), int(n), dtype_code(dtype), int(frame_length), int(hop_length), int(bool(center)),
                                      {"constant": 0, "reflect": 1, "edge": 2, "symmetric": 3}[pad_mode], int(min_period), int(max_period), float(trough_threshold), float(sr), int(mode),
                                      c_void_p(f0_ptr or None), c_void_p(frames_ptr or None), c_void_p(shifts_ptr or None)))
+
+    def pyin_obs_exec(self, cmnd_ptr, shifts_ptr, clips, n_lags, n_frames, thresholds_ptr, beta_ptr, beta_prefix_ptr, boltz_e_ptr, boltz_fact_ptr, n_thresholds, sr, fmin, min_period,
+                      n_pitch_bins, n_bins_per_semitone, no_trough_prob, tiny, log_tiny, log_prob_ptr, voiced_prob_ptr):
+        """pYIN's log observation table [clip][frame][state] and voiced_prob from the CMND and the shifts (``include/librosa_amd.h``: lra_pyin_obs_exec)."""
+        _check(self.lib.lra_pyin_obs_exec(self.handle, c_void_p(cmnd_ptr), c_void_p(shifts_ptr), int(clips), int(n_lags), int(n_frames), c_void_p(thresholds_ptr), c_void_p(beta_ptr),
+                                          c_void_p(beta_prefix_ptr), c_void_p(boltz_e_ptr), c_void_p(boltz_fact_ptr), int(n_thresholds), float(sr), float(fmin), int(min_period),
+                                          int(n_pitch_bins), int(n_bins_per_semitone), float(no_trough_prob), float(tiny), float(log_tiny), c_void_p(log_prob_ptr), c_void_p(voiced_prob_ptr)))
+
+    def pyin_finish_exec(self, states_ptr, n, n_pitch_bins, freqs_ptr, fill_na, f0_ptr, voiced_ptr):
+        """states -> f0 and voiced_flag (``include/librosa_amd.h``: lra_pyin_finish_exec); ``fill_na=None`` keeps the best guess in unvoiced frames."""
+        _check(self.lib.lra_pyin_finish_exec(self.handle, c_void_p(states_ptr), int(n), int(n_pitch_bins), c_void_p(freqs_ptr), int(fill_na is not None),
+                                             0.0 if fill_na is None else float(fill_na), c_void_p(f0_ptr), c_void_p(voiced_ptr)))
 
     VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
     VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits

@@ -8,6 +8,6 @@ from .spectrum import _spectrogram, amplitude_to_db, db_to_amplitude, db_to_powe
 from . import constantq
 from .constantq import cqt, vqt
 from . import pitch
-from .pitch import estimate_tuning, piptrack, pitch_tuning, yin
+from .pitch import estimate_tuning, piptrack, pitch_tuning, pyin, yin
 
-__all__ = ["audio", "constantq", "convert", "intervals", "pitch", "spectrum", "piptrack", "pitch_tuning", "estimate_tuning", "yin", "hz_to_octs", "octs_to_hz", "cqt", "vqt", "interval_frequencies", "stream", "resample", "stft", "istft", "_spectrogram", "magphase", "griffinlim", "phase_vocoder", "pcen", "power_to_db", "amplitude_to_db", "db_to_power", "db_to_amplitude", "hz_to_mel", "mel_to_hz", "fft_frequencies", "tempo_frequencies", "fourier_tempo_frequencies", "mel_frequencies", "frames_to_samples", "samples_to_frames", "frames_to_time", "time_to_frames", "samples_to_time", "time_to_samples"]
+__all__ = ["audio", "constantq", "convert", "intervals", "pitch", "spectrum", "piptrack", "pitch_tuning", "estimate_tuning", "yin", "pyin", "hz_to_octs", "octs_to_hz", "cqt", "vqt", "interval_frequencies", "stream", "resample", "stft", "istft", "_spectrogram", "magphase", "griffinlim", "phase_vocoder", "pcen", "power_to_db", "amplitude_to_db", "db_to_power", "db_to_amplitude", "hz_to_mel", "mel_to_hz", "fft_frequencies", "tempo_frequencies", "fourier_tempo_frequencies", "mel_frequencies", "frames_to_samples", "samples_to_frames", "frames_to_time", "time_to_frames", "samples_to_time", "time_to_samples"]

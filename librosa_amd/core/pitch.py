@@ -1,4 +1,4 @@
-"""``piptrack``, ``pitch_tuning``, ``estimate_tuning`` and ``yin`` with librosa's signatures (``librosa/core/pitch.py:28-628``).
+"""``piptrack``, ``pitch_tuning``, ``estimate_tuning``, ``yin`` and ``pyin`` with librosa's signatures (``librosa/core/pitch.py:28-931``).
 
 The tracker is a three-point stencil along the bins of a magnitude spectrogram that is already on the device (``csrc/lra_pitch.h``):
 ``piptrack`` writes the two dense arrays in one launch (zeros included); ``estimate_tuning`` never forms them -- the same kernel emits only
@@ -21,6 +21,17 @@ Documented difference: ``yin`` with ``frame_length + max_period > 4800`` (no com
 ``ParameterError`` before any device work: the direct kernel keeps 16 bytes per lag in a workgroup's 160 KiB of LDS (sr 44100,
 ``frame_length=16384``, ``fmin=4`` is such a call; the reference accepts it).
 
+``pyin`` runs, per chunk of whole clips sized by ``sequence.SCRATCH_BUDGET``: the same front half on float64 samples (float32 input is widened
+first, on the device for a tensor); one launch of ``csrc/lra_pyin.h``'s observation kernel, which turns the CMND and the shifts into the float64
+log observation table in the decoder's layout and ``voiced_prob`` -- the thresholds, ``beta_probs``, their prefix sums and the two factors of
+SciPy's Boltzmann pmf are host tables built as the reference builds them; ``lra_viterbi_exec`` on that resident table with the reference's
+transition and ``p_init`` (``sequence._ResidentDecoder``); and an elementwise lookup of ``f0`` and ``voiced_flag``.
+
+Documented differences of ``pyin``: the reference's float32 cancellation noise is not reproduced (``pyin(y32)`` equals
+``pyin(y32.astype(float64))``); ``2 * n_pitch_bins > 8192`` (the default range at ``resolution=0.01``), ``n_thresholds`` that is not a positive
+integer, a non-positive ``boltzmann_parameter`` or ``resolution``, and ``8 * (n_pitch_bins + n_thresholds)`` bytes beyond a workgroup's 160 KiB of
+LDS raise ``ParameterError`` before any device work, as ``yin``'s refusal below does.
+
 Documented difference: an ``S`` with fewer than two bins raises ``ParameterError`` (the reference fails incidentally there, with
 ``ZeroDivisionError`` or ``np.gradient``'s ``ValueError``).  ``S`` must be floating-point or complex.
 """
@@ -36,7 +47,7 @@ from ..util.utils import is_torch_tensor, valid_audio
 from . import convert
 from . import spectrum as _spectrum
 
-__all__ = ["piptrack", "pitch_tuning", "estimate_tuning", "yin"]
+__all__ = ["piptrack", "pitch_tuning", "estimate_tuning", "yin", "pyin"]
 
 _YIN_F0, _YIN_FRAMES = 0, 1  # the LRA_YIN_* values
 _YIN_LDS_MAX = 160 * 1024  # LRA_YIN_LDS_MAX
@@ -380,6 +391,11 @@ def _yin_prepare(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode):
 
 def _yin_run(y, mode, fmin, fmax, sr, frame_length, hop_length, trough_threshold, center, pad_mode):
     y, real, hop, center, pad_mode, min_period, max_period = _yin_prepare(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode)
+    return _yin_launch(y, real, mode, sr, frame_length, hop, trough_threshold, center, pad_mode, min_period, max_period)
+
+
+def _yin_launch(y, real, mode, sr, frame_length, hop, trough_threshold, center, pad_mode, min_period, max_period):
+    """One ``lra_yin_exec`` on samples that ``_yin_prepare`` has passed."""
     lead = tuple(int(s) for s in y.shape[:-1])
     n = int(y.shape[-1])
     batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
@@ -418,3 +434,171 @@ def _yin_frames(y, *, fmin, fmax, sr=22050, frame_length=2048, hop_length=None, 
     mean normalised difference function and the parabolic shifts as (..., max_period - min_period + 1, n_frames) arrays of ``y``'s type
     (computed in float64 and rounded once)."""
     return _yin_run(y, _YIN_FRAMES, fmin, fmax, sr, frame_length, hop_length, 0.0, center, pad_mode)
+
+
+def _pyin_tables(n_lags, n_thresholds, beta_parameters, boltzmann_parameter):
+    """The host tables of the observation kernel, built as the reference builds them (``core/pitch.py:802-804``, ``:892-894``): thresholds[1:],
+    beta_probs, np.sum(beta_probs[:m]) for every m, and the two factors of scipy's ``boltzmann._pmf`` = fact[N] * E[k]."""
+    key = (int(n_lags), int(n_thresholds), tuple(float(b) for b in beta_parameters), boltzmann_parameter)
+    if key not in _PYIN_TABLES:
+        import scipy.stats
+
+        thresholds = np.linspace(0, 1, n_thresholds + 1)
+        beta_probs = np.diff(scipy.stats.beta.cdf(thresholds, beta_parameters[0], beta_parameters[1]))
+        prefix = np.array([np.sum(beta_probs[:m]) for m in range(n_thresholds + 1)], dtype=np.float64)
+        lambda_ = np.asarray(boltzmann_parameter)
+        k = np.arange(n_lags + 1)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            e = np.exp(-lambda_ * k).astype(np.float64)
+            fact = ((1 - np.exp(-lambda_)) / (1 - np.exp(-lambda_ * k))).astype(np.float64)
+        fact[0] = 0.0   # (no trough below the threshold: never read)
+        if len(_PYIN_TABLES) >= 8:
+            _PYIN_TABLES.clear()
+        _PYIN_TABLES[key] = (np.ascontiguousarray(thresholds[1:]), np.ascontiguousarray(beta_probs, dtype=np.float64), prefix, e, fact)
+    return _PYIN_TABLES[key]
+
+
+_PYIN_TABLES = {}
+_PYIN_DECODERS = {}
+_PYIN_LDS_MAX = 160 * 1024  # LRA_PYIN_LDS_MAX
+
+
+def _pyin_bins(fmin, fmax, resolution, n_thresholds, boltzmann_parameter):
+    """``n_bins_per_semitone`` and ``n_pitch_bins`` (``core/pitch.py:806-807``), and the limits of the device path, before any device work."""
+    from .. import sequence as _sequence
+
+    if isinstance(n_thresholds, (bool, np.bool_)) or not isinstance(n_thresholds, (int, np.integer)) or n_thresholds < 1:
+        raise ParameterError(f"n_thresholds={n_thresholds!r} must be a positive integer")
+    if not (_is_number(boltzmann_parameter) and boltzmann_parameter > 0):
+        raise ParameterError(f"boltzmann_parameter={boltzmann_parameter!r} must be a positive number")
+    if not (_is_number(resolution) and resolution > 0):
+        raise ParameterError(f"resolution={resolution!r} must be a positive number")
+    n_bins_per_semitone = int(np.ceil(1.0 / resolution))
+    n_pitch_bins = int(np.floor(12 * n_bins_per_semitone * np.log2(fmax / fmin))) + 1
+    _sequence._check_states(2 * n_pitch_bins)   # documented difference: the decoder's limit
+    if _native.load_library().lra_pyin_lds_bytes(n_pitch_bins, int(n_thresholds)) > _PYIN_LDS_MAX:
+        # documented difference: a frame's voiced row and two counters per threshold live in the LDS of one workgroup
+        raise ParameterError(f"n_thresholds={n_thresholds} with {n_pitch_bins} pitch bins is too large for the device: 8 bytes per pitch bin and per threshold must fit {_PYIN_LDS_MAX} bytes")
+    return n_bins_per_semitone, n_pitch_bins
+
+
+def _pyin_obs(sess, cm_ptr, sh_ptr, clips, n_lags, n_frames, log_prob_ptr, voiced_ptr, *, sr, fmin, min_period, n_thresholds, beta_parameters, boltzmann_parameter, n_pitch_bins,
+              n_bins_per_semitone, no_trough_prob):
+    """One launch of the observation kernel on resident float64 CMND and shifts [clip][lag][frame]."""
+    from ..util.utils import tiny
+
+    up = lambda a: sess.input_raw(_spectrum._as_like(sess, a), np.float64)
+    thresholds, beta_probs, prefix, e, fact = _pyin_tables(n_lags, n_thresholds, beta_parameters, boltzmann_parameter)
+    eps = tiny(np.empty(0, dtype=np.float64))
+    sess.ctx.pyin_obs_exec(cm_ptr, sh_ptr, clips, n_lags, n_frames, up(thresholds), up(beta_probs), up(prefix), up(e), up(fact), int(n_thresholds), float(sr), float(fmin), int(min_period),
+                           n_pitch_bins, n_bins_per_semitone, float(no_trough_prob), float(eps), float(np.log(0.0 + eps)), log_prob_ptr, voiced_ptr)
+
+
+def _pyin_log_prob(yin_frames, parabolic_shifts, *, sr, fmin, fmax, min_period, n_thresholds=100, beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1, no_trough_prob=0.01):
+    """The observation stage of ``pyin`` alone (``core/pitch.py:796-825``, ``__pyin_helper``) on arrays as given: ``yin_frames`` and
+    ``parabolic_shifts`` of shape (..., n_lags, n_frames).  Returns ``log(observation_probs + tiny)`` (..., 2 * n_pitch_bins, n_frames) -- a view of
+    the decoder's own (..., n_frames, 2 * n_pitch_bins) layout -- and ``voiced_prob`` (..., n_frames), float64."""
+    n_bins_per_semitone, n_pitch_bins = _pyin_bins(fmin, fmax, resolution, n_thresholds, boltzmann_parameter)
+    if tuple(yin_frames.shape) != tuple(parabolic_shifts.shape) or yin_frames.ndim < 2 or yin_frames.shape[-2] < 2:
+        raise ParameterError(f"yin_frames.shape={tuple(yin_frames.shape)} and parabolic_shifts.shape={tuple(parabolic_shifts.shape)} must be equal, (..., n_lags >= 2, n_frames)")
+    lead = tuple(int(s) for s in yin_frames.shape[:-2])
+    n_lags, n_frames = int(yin_frames.shape[-2]), int(yin_frames.shape[-1])
+    clips = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    sess = _arrays.Session(yin_frames)
+    try:
+        lp_ptr, lp_h = sess.output((clips, n_frames, 2 * n_pitch_bins), np.float64)
+        vp_ptr, vp_h = sess.output((clips, n_frames), np.float64)
+        if clips * n_frames > 0:
+            _pyin_obs(sess, sess.input_raw(yin_frames, np.float64), sess.input_raw(parabolic_shifts, np.float64), clips, n_lags, n_frames, lp_ptr, vp_ptr, sr=sr, fmin=fmin,
+                      min_period=min_period, n_thresholds=n_thresholds, beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter, n_pitch_bins=n_pitch_bins,
+                      n_bins_per_semitone=n_bins_per_semitone, no_trough_prob=no_trough_prob)
+        log_prob, voiced_prob = sess.result(lp_h), sess.result(vp_h)
+    finally:
+        sess.close()
+    return _arrays.swap_last_two(log_prob.reshape(lead + (n_frames, 2 * n_pitch_bins))), voiced_prob.reshape(lead + (n_frames,))
+
+
+def _pyin_decoder(n_pitch_bins, n_bins_per_semitone, max_transition_rate, hop, sr, switch_prob, transition_min_prob):
+    """The decoder of the reference's transition and ``p_init`` (``core/pitch.py:827-842``); its host tables are kept for the next call."""
+    from .. import sequence as _sequence
+
+    key = (n_pitch_bins, n_bins_per_semitone, max_transition_rate, hop, sr, switch_prob, transition_min_prob)
+    if key not in _PYIN_DECODERS:
+        max_semitones_per_frame = round(max_transition_rate * 12 * hop / sr)
+        transition_width = max_semitones_per_frame * n_bins_per_semitone + 1
+        transition = _sequence.transition_local(n_pitch_bins, transition_width, window="triangle", wrap=False)
+        transition = np.kron(_sequence.transition_loop(2, 1 - switch_prob), transition)
+        p_init = np.ones(2 * n_pitch_bins) / (2 * n_pitch_bins)
+        decoder = _sequence._ResidentDecoder(transition, p_init, transition_min_prob)
+        if len(_PYIN_DECODERS) >= 4:
+            _PYIN_DECODERS.clear()
+        _PYIN_DECODERS[key] = decoder
+    return _PYIN_DECODERS[key]
+
+
+def _pyin_run(y, fmin, fmax, sr, frame_length, hop_length, n_thresholds, beta_parameters, boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob, fill_na, center,
+              pad_mode, transition_min_prob):
+    from .. import sequence as _sequence
+
+    y, real, hop, center, pad_mode, min_period, max_period = _yin_prepare(y, fmin, fmax, sr, frame_length, hop_length, center, pad_mode)
+    n_bins_per_semitone, n_pitch_bins = _pyin_bins(fmin, fmax, resolution, n_thresholds, boltzmann_parameter)
+    n_states = 2 * n_pitch_bins
+    decoder = _pyin_decoder(n_pitch_bins, n_bins_per_semitone, max_transition_rate, hop, sr, switch_prob, transition_min_prob)
+    freqs = fmin * 2 ** (np.arange(n_pitch_bins) / (12 * n_bins_per_semitone))
+    lead = tuple(int(s) for s in y.shape[:-1])
+    n = int(y.shape[-1])
+    batch = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    n_frames = 1 + (n + (2 * (frame_length // 2) if center else 0) - frame_length) // hop
+    n_lags = max_period - min_period + 1
+    f64 = np.dtype(np.float64)
+    y = _arrays.cast(y, f64).reshape((batch, n))   # float32 samples are widened exactly: the front half computes in float64 after the load anyway
+    # whole clips per chunk: the front half (16 bytes per lag and frame), log_prob (8 per state and step) and the pointer scratch (2)
+    per_clip = (16 * n_lags + 10 * n_states) * n_frames
+    chunk = int(max(1, min(batch, _sequence.SCRATCH_BUDGET // per_clip)))
+    parts = []
+    for c0 in range(0, max(batch, 1), chunk):   # (an empty batch takes the same path: every native call answers an empty one)
+        c1 = min(batch, c0 + chunk)
+        clips = c1 - c0
+        cm, sh, _ = _yin_launch(y[c0:c1], f64, _YIN_FRAMES, sr, frame_length, hop, 0.0, center, pad_mode, min_period, max_period)
+        sess = _arrays.Session(cm)
+        try:
+            lp_ptr = sess.scratch(8 * clips * n_states * n_frames)
+            ptr_ptr = sess.scratch(2 * clips * n_states * n_frames)
+            vp_ptr, vp_h = sess.output((clips, n_frames), np.float64)
+            f0_ptr, f0_h = sess.output((clips, n_frames), np.float64)
+            flag_ptr, flag_h = sess.output((clips, n_frames), np.uint8)
+            _pyin_obs(sess, sess.input_raw(cm, f64), sess.input_raw(sh, f64), clips, n_lags, n_frames, lp_ptr, vp_ptr, sr=sr, fmin=fmin, min_period=min_period, n_thresholds=n_thresholds,
+                      beta_parameters=beta_parameters, boltzmann_parameter=boltzmann_parameter, n_pitch_bins=n_pitch_bins, n_bins_per_semitone=n_bins_per_semitone,
+                      no_trough_prob=no_trough_prob)
+            del cm, sh
+            states_ptr, _ = decoder.run(sess, lp_ptr, ptr_ptr, clips, n_frames)
+            sess.ctx.pyin_finish_exec(states_ptr, clips * n_frames, n_pitch_bins, sess.input_raw(_spectrum._as_like(sess, freqs), f64), fill_na, f0_ptr, flag_ptr)
+            parts.append((sess.result(f0_h), sess.result(flag_h), sess.result(vp_h)))
+        finally:
+            sess.close()
+    if len(parts) > 1:
+        if is_torch_tensor(parts[0][0]):
+            import torch
+
+            parts = [tuple(torch.cat([p[i] for p in parts]) for i in range(3))]
+        else:
+            parts = [tuple(np.concatenate([p[i] for p in parts]) for i in range(3))]
+    f0, flag, voiced_prob = parts[0]
+    if is_torch_tensor(flag):
+        import torch
+
+        flag = flag.view(torch.bool)
+    else:
+        flag = flag.view(np.bool_)
+    return f0.reshape(lead + (n_frames,)), flag.reshape(lead + (n_frames,)), voiced_prob.reshape(lead + (n_frames,))
+
+
+def pyin(y, *, fmin, fmax, sr=22050, frame_length=2048, hop_length=None, n_thresholds=100, beta_parameters=(2, 18), boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92,
+         switch_prob=0.01, no_trough_prob=0.01, fill_na=np.nan, center=True, pad_mode="constant", transition_min_prob=1e-4):
+    """Fundamental frequency estimation with probabilistic YIN; drop-in for ``librosa.pyin`` (``core/pitch.py:631-852``).
+
+    ``y``: (..., n) NumPy array or device tensor, float32 or float64.  Returns ``(f0, voiced_flag, voiced_prob)`` of shape (..., n_frames): float64,
+    bool and float64, NumPy arrays for NumPy input and device tensors for a device tensor.  ``y`` is never written.  See the module docstring
+    for the pipeline and the documented differences."""
+    return _pyin_run(y, fmin, fmax, sr, frame_length, hop_length, n_thresholds, beta_parameters, boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob, fill_na,
+                     center, pad_mode, transition_min_prob)

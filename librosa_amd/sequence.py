@@ -84,32 +84,70 @@ def _as_real(prob):
     return _arrays.cast(prob, real), real, epsilon
 
 
-def _decode(x, kind, real, epsilon, n_states, n_steps, chains, log_trans, log_p_init, log_marginal, threshold, n_labels, flag_check):
-    """x: (chains, n_states, n_steps) (binary: (chains, n_steps)) array or tensor of ``real``; the tables float64 on the host: log_trans
-    (n_tables, n_states, n_states), log_p_init (n_tables, n_states).  Returns states (chains, n_steps) uint16 and logp (chains,) float64."""
+def _search_tables(log_trans, log_p_init, threshold, n_states):
+    """The tables as contiguous float64 and, for a thresholded search above ``_SMALL_MAX`` states, the predecessor lists (else None); every
+    table's empty-list check, in label order, before any device work."""
     log_trans = np.ascontiguousarray(log_trans, dtype=np.float64)
     log_p_init = np.ascontiguousarray(log_p_init, dtype=np.float64)
-    n_tables = log_trans.shape[0]
     lists = None
     if np.isfinite(threshold):
-        for table in log_trans:   # (every table's empty-list check, in label order, before any device work)
+        for table in log_trans:
             if n_states > _SMALL_MAX:
                 lists = _predecessors(table, threshold)
             else:
                 empty = np.flatnonzero(~(table >= threshold).any(axis=0))
                 if empty.size:
                     raise ParameterError(f"Empty transition matrix detected for state {int(empty[0])} in Viterbi. Try reducing your minimum transition probability threshold.")
+    return log_trans, log_p_init, lists
+
+
+def _upload_tables(sess, log_trans, log_p_init, log_marginal, lists):
+    """Device pointers of what ``lra_viterbi_exec`` reads: (log_trans or 0, log_p_init, log_marginal or 0, pred_k, pred_lt, pred_n, n_pred)."""
+    host = lambda a, dtype: sess.input_raw(_as_like(sess, np.ascontiguousarray(a, dtype=dtype)), dtype)
+    lt_ptr = host(log_trans, np.float64) if lists is None else 0
+    pi_ptr = host(log_p_init, np.float64)
+    lm_ptr = host(log_marginal, np.float64) if log_marginal is not None else 0
+    k_ptr, plt_ptr, n_ptr = (host(lists[0], np.uint16), host(lists[1], np.float64), host(lists[2], np.int32)) if lists is not None else (0, 0, 0)
+    return lt_ptr, pi_ptr, lm_ptr, k_ptr, plt_ptr, n_ptr, lists[0].shape[0] if lists is not None else 0
+
+
+class _ResidentDecoder:
+    """``viterbi``'s decode of a log observation table that is already on the device in the kernel's layout [chain][step][state] (``pyin``'s
+    observation stage writes it there): the tables of ``viterbi(prob, transition, p_init=p_init, transition_min_prob=...)`` for float64 ``prob``
+    built once on the host, every check before device work; ``run`` uploads them into a session and launches ``lra_viterbi_exec`` alone."""
+
+    def __init__(self, transition, p_init, transition_min_prob):
+        n_states = int(transition.shape[0])
+        _check_states(n_states)
+        _check_transition(transition, n_states)
+        epsilon = tiny(np.empty(0, dtype=np.float64))
+        p_init = _check_p_init(p_init, n_states)
+        self.n_states = n_states
+        self.threshold = _threshold(transition_min_prob, epsilon)
+        self.log_trans, self.log_p_init, self.lists = _search_tables(np.log(transition + epsilon)[None], np.log(p_init + epsilon)[None], self.threshold, n_states)
+        if self.lists is not None:
+            self.log_trans = None   # (the lists carry every entry the search reads)
+
+    def run(self, sess, log_prob_ptr, ptr_ptr, chains, n_steps):
+        """Returns the handle of the states (chains, n_steps) uint16; ``ptr_ptr``: 2 bytes per chain, step and state of scratch."""
+        lt_ptr, pi_ptr, _, k_ptr, plt_ptr, n_ptr, n_pred = _upload_tables(sess, self.log_trans, self.log_p_init, None, self.lists)
+        states_ptr, states_h = sess.output((chains, n_steps), np.uint16)
+        logp_ptr = sess.scratch(8 * max(chains, 1))
+        sess.ctx.viterbi_exec(log_prob_ptr, chains, self.n_states, n_steps, lt_ptr, pi_ptr, 1, float(self.threshold), n_pred, k_ptr, plt_ptr, n_ptr, ptr_ptr, states_ptr, logp_ptr)
+        return states_ptr, states_h
+
+
+def _decode(x, kind, real, epsilon, n_states, n_steps, chains, log_trans, log_p_init, log_marginal, threshold, n_labels, flag_check):
+    """x: (chains, n_states, n_steps) (binary: (chains, n_steps)) array or tensor of ``real``; the tables float64 on the host: log_trans
+    (n_tables, n_states, n_states), log_p_init (n_tables, n_states).  Returns states (chains, n_steps) uint16 and logp (chains,) float64."""
+    log_trans, log_p_init, lists = _search_tables(log_trans, log_p_init, threshold, n_states)
+    n_tables = log_trans.shape[0]
     if n_steps < 1:
         raise ParameterError(f"prob must hold at least one step, given n_steps={n_steps}")
     sess = _arrays.Session(x)
     try:
         ctx = sess.ctx
-        host = lambda a, dtype: sess.input_raw(_as_like(sess, np.ascontiguousarray(a, dtype=dtype)), dtype)
-        lt_ptr = host(log_trans, np.float64) if lists is None else 0
-        pi_ptr = host(log_p_init, np.float64)
-        lm_ptr = host(log_marginal, np.float64) if log_marginal is not None else 0
-        k_ptr, plt_ptr, n_ptr = (host(lists[0], np.uint16), host(lists[1], np.float64), host(lists[2], np.int32)) if lists is not None else (0, 0, 0)
-        n_pred = lists[0].shape[0] if lists is not None else 0
+        lt_ptr, pi_ptr, lm_ptr, k_ptr, plt_ptr, n_ptr, n_pred = _upload_tables(sess, log_trans, log_p_init, log_marginal, lists)
         states_ptr, states_h = sess.output((chains, n_steps), np.uint16)
         logp_ptr, logp_h = sess.output((chains,), np.float64)
         per_chain = 10 * n_states * n_steps
