@@ -456,6 +456,48 @@ int lra_viterbi_prep_exec(lra_ctx* ctx, const void* prob, int dtype, int kind, i
 int lra_viterbi_exec(lra_ctx* ctx, const void* log_prob, int64_t chains, int n_states, int64_t n_steps, const void* log_trans, const void* log_p_init, int n_tables, double threshold,
                      int n_pred, const void* pred_k, const void* pred_lt, const void* pred_n, void* ptr, void* states, void* logp);
 
+/* ---- sequence.dtw and dtw_backtracking: librosa/sequence.py:185-694 ----------------------------------------------------------------------- */
+#define LRA_DTW_MAX_STEPS 16 /* rows of a step table, the three defaults (1, 1), (0, 1), (1, 0) included */
+#define LRA_DTW_MAX_STEP 8   /* the largest step component */
+#define LRA_DTW_EUCLIDEAN 0
+#define LRA_DTW_SQEUCLIDEAN 1
+#define LRA_DTW_CITYBLOCK 2
+#define LRA_DTW_COSINE 3
+#define LRA_DTW_I32 2 /* types of a given C besides LRA_F32 and LRA_F64 */
+#define LRA_DTW_I64 3
+#define LRA_DTW_U8 4
+#define LRA_DTW_FLAG_NAN 1         /* C holds a NaN */
+#define LRA_DTW_FLAG_END_INF 2     /* D[-1, -1] is infinite (no subseq) */
+#define LRA_DTW_FLAG_ROW_INF 4     /* every entry of D[-1] is infinite (subseq) */
+#define LRA_DTW_FLAG_NOT_ORIGIN 8  /* the path does not end at (0, 0) (no subseq) */
+#define LRA_DTW_FLAG_BAD_STEP 16   /* the step matrix holds an index outside the step table */
+#define LRA_DTW_START_END (-1)     /* backtrack from (N - 1, M - 1) */
+#define LRA_DTW_START_ARGMIN (-2)  /* backtrack from (N - 1, np.argmin(D[-1])) */
+/* Bytes of LDS a tile of lra_dtw_accumulate_exec needs (host arithmetic only): D with its halo, C and the step indices of a tile of edge `tile`
+ * (0: the library's choice).  0 for arguments the accumulation refuses. */
+int64_t lra_dtw_lds_bytes(int tile, int max_0, int max_1);
+/* C[n][m] = metric(X[:, n], Y[:, m]) in float64 (device, [N][M]) from X [n_features][N] and Y [n_features][M] of `dtype` (device, never
+ * written), the features summed in ascending order; a zero vector under LRA_DTW_COSINE gives NaN.  work: 16 bytes (device).  *flags:
+ * LRA_DTW_FLAG_NAN where C holds one (this waits for the stream). */
+int lra_dtw_cost_exec(lra_ctx* ctx, const void* X, const void* Y, int dtype, int64_t n_features, int64_t N, int64_t M, int metric, void* C, void* work, int* flags);
+/* A given C of `dtype` (LRA_F32, LRA_F64, LRA_DTW_I32, LRA_DTW_I64, LRA_DTW_U8; `count` elements, device, never written) -> float64 in `out`,
+ * and the NaN flag as above.  out may be NULL for LRA_F64: the check alone. */
+int lra_dtw_prepare_exec(lra_ctx* ctx, const void* C, int dtype, int64_t count, void* out, void* work, int* flags);
+/* __dtw_calc_accu_cost (:502-571) of C float64 [N][M] (device): D float64 [N][M] and the index of the step that reached each cell, uint8 [N][M]
+ * (0 where none improved it).  steps: int32 [n_steps][2], weights_add, weights_mul: float64 [n_steps] (HOST arrays).  D starts at +inf, at
+ * C[0][0] in (0, 0) and, with subseq, at C[0][:] in the first row.  band: C reads as +inf where m - n >= band_hi or m - n <= band_lo.  tile: 0
+ * for the library's choice, or 8, 16, 32 or 64; the result does not depend on it.  One launch per tile anti-diagonal, in stream order. */
+int lra_dtw_accumulate_exec(lra_ctx* ctx, const void* C, int64_t N, int64_t M, const int32_t* steps, const double* weights_add, const double* weights_mul, int n_steps, int subseq, int band,
+                            int64_t band_lo, int64_t band_hi, int tile, void* D, void* step_idx);
+/* uint8 step indices -> int32, `count` elements (device). */
+int lra_dtw_widen_exec(lra_ctx* ctx, const void* step_idx, int64_t count, void* out);
+/* __dtw_backtracking (:575-640) over step_idx [N][M] (uint8, or int32 with steps_i32; device) and the step table steps int32 [n_steps][2]
+ * (HOST): from column `start` of the last row (or LRA_DTW_START_*), until row 0 (subseq) or (0, 0), or until an index goes negative.  D: float64
+ * [N][M] or NULL; with it the LRA_DTW_FLAG_END_INF / ROW_INF checks are made first and a flagged call writes no path.  path: int64
+ * [N + M - 1][2] (device); work: 16 bytes (device).  *length: pairs written; *status: the flags met (this waits for the stream). */
+int lra_dtw_backtrack_exec(lra_ctx* ctx, const void* D, const void* step_idx, int steps_i32, int64_t N, int64_t M, const int32_t* steps, int n_steps, int subseq, int64_t start, void* path,
+                           void* work, int64_t* length, int* status);
+
 /* ---- the back half of pyin around the decode: librosa.pyin, librosa/core/pitch.py:796-852 and __pyin_helper :855-931 ---------------------- */
 #define LRA_PYIN_LDS_MAX (160 * 1024)
 /* Bytes of LDS a workgroup of lra_pyin_obs_exec needs (host arithmetic only): per frame the voiced row (8 n_pitch_bins) and two counters per

@@ -124,6 +124,12 @@ SIGNATURES = {
     "lra_viterbi_lds_bytes": (c_int64, [c_int, c_int]),
     "lra_viterbi_prep_exec": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_double, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int)]),
     "lra_viterbi_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lra_dtw_lds_bytes": (c_int64, [c_int, c_int, c_int]),
+    "lra_dtw_cost_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "lra_dtw_prepare_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, POINTER(c_int)]),
+    "lra_dtw_accumulate_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "lra_dtw_widen_exec": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "lra_dtw_backtrack_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int)]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -665,6 +671,48 @@ class Context:
         """states -> f0 and voiced_flag (``include/librosa_amd.h``: lra_pyin_finish_exec); ``fill_na=None`` keeps the best guess in unvoiced frames."""
         _check(self.lib.lra_pyin_finish_exec(self.handle, c_void_p(states_ptr), int(n), int(n_pitch_bins), c_void_p(freqs_ptr), int(fill_na is not None),
                                              0.0 if fill_na is None else float(fill_na), c_void_p(f0_ptr), c_void_p(voiced_ptr)))
+
+    DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}   # the LRA_DTW_* metrics
+    DTW_TYPES = {"float32": 0, "float64": 1, "int32": 2, "int64": 3, "uint8": 4}      # what lra_dtw_prepare_exec reads
+    DTW_FLAG_NAN, DTW_FLAG_END_INF, DTW_FLAG_ROW_INF, DTW_FLAG_NOT_ORIGIN, DTW_FLAG_BAD_STEP = 1, 2, 4, 8, 16   # the LRA_DTW_FLAG_* bits
+    DTW_START_END, DTW_START_ARGMIN = -1, -2
+
+    def dtw_cost_exec(self, x_ptr, y_ptr, dtype, n_features, n, m, metric, c_ptr, work_ptr):
+        """The float64 cost matrix of two feature sequences (``include/librosa_amd.h``: lra_dtw_cost_exec).  Returns the flags met (this waits
+        for the stream)."""
+        flags = c_int(0)
+        _check(self.lib.lra_dtw_cost_exec(self.handle, c_void_p(x_ptr), c_void_p(y_ptr), dtype_code(dtype), int(n_features), int(n), int(m), int(metric), c_void_p(c_ptr),
+                                          c_void_p(work_ptr), byref(flags)))
+        return int(flags.value)
+
+    def dtw_prepare_exec(self, c_ptr, dtype, count, out_ptr, work_ptr):
+        """A given cost matrix as float64, and its NaN flag (lra_dtw_prepare_exec); ``out_ptr`` 0: the check alone (float64)."""
+        flags = c_int(0)
+        _check(self.lib.lra_dtw_prepare_exec(self.handle, c_void_p(c_ptr), int(self.DTW_TYPES[np.dtype(dtype).name]), int(count), c_void_p(out_ptr or None), c_void_p(work_ptr),
+                                             byref(flags)))
+        return int(flags.value)
+
+    def dtw_accumulate_exec(self, c_ptr, n, m, steps, weights_add, weights_mul, subseq, band, tile, d_ptr, step_idx_ptr):
+        """The accumulated cost matrix and the uint8 step indices (lra_dtw_accumulate_exec); ``steps`` int32 (n_steps, 2), the weights float64,
+        host arrays; ``band``: None or (band_lo, band_hi)."""
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        weights_add, weights_mul = np.ascontiguousarray(weights_add, dtype=np.float64), np.ascontiguousarray(weights_mul, dtype=np.float64)
+        lo, hi = band if band is not None else (0, 0)
+        _check(self.lib.lra_dtw_accumulate_exec(self.handle, c_void_p(c_ptr), int(n), int(m), c_void_p(steps.ctypes.data), c_void_p(weights_add.ctypes.data),
+                                                c_void_p(weights_mul.ctypes.data), int(steps.shape[0]), int(bool(subseq)), int(band is not None), int(lo), int(hi), int(tile), c_void_p(d_ptr),
+                                                c_void_p(step_idx_ptr)))
+
+    def dtw_widen_exec(self, step_idx_ptr, count, out_ptr):
+        """uint8 step indices -> int32 (lra_dtw_widen_exec)."""
+        _check(self.lib.lra_dtw_widen_exec(self.handle, c_void_p(step_idx_ptr), int(count), c_void_p(out_ptr)))
+
+    def dtw_backtrack_exec(self, d_ptr, step_idx_ptr, steps_i32, n, m, steps, subseq, start, path_ptr, work_ptr):
+        """The warping path (lra_dtw_backtrack_exec).  Returns (length, status) (this waits for the stream)."""
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        length, status = c_int64(0), c_int(0)
+        _check(self.lib.lra_dtw_backtrack_exec(self.handle, c_void_p(d_ptr or None), c_void_p(step_idx_ptr), int(bool(steps_i32)), int(n), int(m), c_void_p(steps.ctypes.data),
+                                               int(steps.shape[0]), int(bool(subseq)), int(start), c_void_p(path_ptr), c_void_p(work_ptr), byref(length), byref(status)))
+        return int(length.value), int(status.value)
 
     VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
     VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits

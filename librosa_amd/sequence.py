@@ -9,6 +9,19 @@ flags on ``prob`` that are read before the decode is launched.  Every sequence o
 Differences from the reference: ``n_states`` above ``MAX_STATES`` raises ``ParameterError`` (a sequence's two value rows live
 in the LDS of one workgroup); ``prob`` must be float32 or float64 (other types are converted as NumPy's promotion with ``tiny(prob)`` would);
 a float32 ``p_state`` is widened before it is subtracted.
+
+``dtw`` and ``dtw_backtracking`` (``librosa/sequence.py:185-694``) have the reference's signatures, check order, messages and return shapes.  The
+step table and its weights are built here as the reference builds them; the cost matrix (``dtw_cost``, or ``dtw_prepare`` for a given ``C``),
+the accumulated cost matrix (``dtw_accumulate``: square tiles, one launch per tile anti-diagonal) and the warping path (``dtw_backtrack``) are
+computed on the device (``csrc/lra_dtw.h``).  The checks that need signal-sized data -- NaN in ``C``, ``D[-1, -1]`` infinite, every entry of
+``D[-1]`` infinite, a path that does not end at ``(0, 0)`` -- come back as status words and raise the reference's texts.  Given ``C``, the
+results are the reference's bit for bit; given ``X`` and ``Y``, the device's own cost matrix is within rounding of scipy's.
+
+Differences from the reference for DTW: ``metric`` is one of ``euclidean``, ``sqeuclidean``, ``cityblock``, ``cosine`` (anything
+else raises ``ParameterError``: there is no CPU fallback); the features of ``X`` / ``Y`` are summed in ``X.reshape(-1, N)``'s order; a step
+``(0, 0)`` is refused; at most ``DTW_MAX_STEPS`` = 16 steps with the three defaults and no step component above ``DTW_MAX_STEP`` = 8;
+``dtw_backtracking`` on a ``steps`` matrix holding an index outside the step table, or with ``start`` outside the columns, raises
+``ParameterError`` where the reference raises ``IndexError``.
 """
 from __future__ import annotations
 
@@ -19,7 +32,7 @@ from .filters import get_window
 from .util.exceptions import ParameterError
 from .util.utils import is_positive_int, is_torch_tensor, pad_center, tiny
 
-__all__ = ["viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local"]
+__all__ = ["dtw", "dtw_backtracking", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local"]
 
 MAX_STATES = 8192            # LRA_VITERBI_MAX_STATES
 _SMALL_MAX = 32              # LRA_VITERBI_SMALL_MAX: up to here the threshold is a comparison in the kernel, beyond it a list
@@ -402,3 +415,208 @@ def transition_local(n_states, width, *, window="triangle", wrap=False):
         transition[i] = trans_row
     transition /= transition.sum(axis=1, keepdims=True)
     return transition
+
+
+# ---- dynamic time warping (librosa/sequence.py:185-694) -----------------------------------------------------------------------------------------
+DTW_MAX_STEPS = 16           # LRA_DTW_MAX_STEPS: rows of the step table, the three defaults included
+DTW_MAX_STEP = 8             # LRA_DTW_MAX_STEP: the largest step component
+DTW_METRICS = ("euclidean", "sqeuclidean", "cityblock", "cosine")
+DTW_TILE = 0                 # the accumulate kernel's tile edge: 0 for the library's choice, or 8, 16, 32, 64 (tests reach many-tile grids at tiny shapes)
+_CDIST_TEXT = ("scipy.spatial.distance.cdist returned an error.\n"
+               "Please provide your input in the form X.shape=(K, N) "
+               "and Y.shape=(K, M).\n 1-dimensional sequences should "
+               "be reshaped to X.shape=(1, N) and Y.shape=(1, M).")
+_NO_PATH_TEXT = "No valid sub-sequence warping path could be constructed with the given step sizes."
+
+
+def _dtw_default_steps():
+    return np.array([[1, 1], [0, 1], [1, 0]], dtype=np.uint32)
+
+
+def _dtw_device_limits(step_sizes_sigma):
+    """The documented differences of the step table: the int64 table the kernels take, or ParameterError."""
+    steps = np.asarray(step_sizes_sigma)
+    if steps.ndim != 2 or steps.shape[1] != 2 or np.any(steps != np.floor(steps)):
+        raise ParameterError(f"step_sizes_sigma must be an integer array of shape (n, 2), given shape {steps.shape}")
+    steps = steps.astype(np.int64)
+    if np.any((steps == 0).all(axis=1)):
+        raise ParameterError("step_sizes_sigma cannot contain the step (0, 0): the device's wavefront has no order for it")
+    if len(steps) > DTW_MAX_STEPS:
+        raise ParameterError(f"step_sizes_sigma holds {len(steps)} steps with the three defaults: at most {DTW_MAX_STEPS} are served")
+    if steps.max() > DTW_MAX_STEP:
+        raise ParameterError(f"step_sizes_sigma holds a step component of {int(steps.max())}: at most {DTW_MAX_STEP} is served")
+    return steps
+
+
+def _atleast_2d(a):
+    if is_torch_tensor(a):
+        return a.reshape((1,) * (2 - a.ndim) + tuple(a.shape)) if a.ndim < 2 else a
+    return np.atleast_2d(a)
+
+
+def _same_kind(sess, a):
+    """``a`` as the session's kind of array."""
+    if sess.is_torch:
+        return a.to(sess.device) if is_torch_tensor(a) else _as_like(sess, np.ascontiguousarray(a))
+    return _host(a)
+
+
+def _dtw_features(X):
+    """(..., K, N) -> (features, N) in ``X.reshape(-1, N)``'s order, float32 or float64."""
+    X = _atleast_2d(X)
+    n = int(X.shape[-1])
+    X = X.reshape((-1, n))
+    return X if np.dtype(_arrays.numpy_dtype_of(X)) in (np.dtype(np.float32), np.dtype(np.float64)) else _arrays.cast(X, np.float64)
+
+
+def dtw(X=None, Y=None, *, C=None, metric="euclidean", step_sizes_sigma=None, weights_add=None, weights_mul=None, subseq=False, backtrack=True, global_constraints=False, band_rad=0.25,
+        return_steps=False):
+    """Dynamic time warping (``librosa/sequence.py:185-498``): the cost matrix of ``X`` (..., K, N) and ``Y`` (..., K, M) (or a given ``C``), the
+    accumulated cost matrix ``D`` (float64), the warping path ``wp`` (int64, (L, 2); with ``backtrack``) and the step matrix ``steps`` (int32; with
+    ``return_steps``), all computed on the device.  NumPy input gives NumPy results, tensors on the device give tensors there; the input is never
+    written.  Differences from the reference: the module docstring."""
+    default_steps = _dtw_default_steps()
+    default_weights_add = np.zeros(3, dtype=np.float64)
+    default_weights_mul = np.ones(3, dtype=np.float64)
+    if step_sizes_sigma is None:
+        step_sizes_sigma = default_steps
+        if weights_add is None:
+            weights_add = default_weights_add
+        if weights_mul is None:
+            weights_mul = default_weights_mul
+    else:
+        step_sizes_sigma = _host(step_sizes_sigma)
+        if weights_add is None:
+            weights_add = np.zeros(len(step_sizes_sigma), dtype=np.float64)
+        if weights_mul is None:
+            weights_mul = np.ones(len(step_sizes_sigma), dtype=np.float64)
+        # the defaults get infinite weights (inf * 0.0 is NaN and loses every <, as on the host)
+        default_weights_add.fill(np.inf)
+        default_weights_mul.fill(np.inf)
+        step_sizes_sigma = np.concatenate((default_steps, step_sizes_sigma))
+        weights_add = np.concatenate((default_weights_add, _host(weights_add)))
+        weights_mul = np.concatenate((default_weights_mul, _host(weights_mul)))
+    weights_add, weights_mul = _host(weights_add), _host(weights_mul)
+
+    if np.any(step_sizes_sigma < 0):
+        raise ParameterError("step_sizes_sigma cannot contain negative values")
+    if len(step_sizes_sigma) != len(weights_add):
+        raise ParameterError("len(weights_add) must be equal to len(step_sizes_sigma)")
+    if len(step_sizes_sigma) != len(weights_mul):
+        raise ParameterError("len(weights_mul) must be equal to len(step_sizes_sigma)")
+    if C is None and (X is None or Y is None):
+        raise ParameterError("If C is not supplied, both X and Y must be supplied")
+    if C is not None and (X is not None or Y is not None):
+        raise ParameterError("If C is supplied, both X and Y must not be supplied")
+    steps_table = _dtw_device_limits(step_sizes_sigma)
+
+    c_is_transposed = False
+    if C is None:
+        if metric not in DTW_METRICS:
+            raise ParameterError(f"metric={metric!r} is not served on the device: one of {', '.join(DTW_METRICS)}")
+        X, Y = _dtw_features(X), _dtw_features(Y)
+        if int(X.shape[0]) != int(Y.shape[0]):
+            raise ParameterError(_CDIST_TEXT)
+        if subseq and int(X.shape[1]) > int(Y.shape[1]):
+            X, Y = Y, X   # C.T: every metric served gives the same bits with its arguments exchanged
+            c_is_transposed = True
+        n, m = int(X.shape[1]), int(Y.shape[1])
+        like = X if is_torch_tensor(X) or not is_torch_tensor(Y) else Y
+    else:
+        C = _atleast_2d(C)
+        if C.ndim != 2:
+            raise ParameterError(f"C must be a matrix, given shape {tuple(C.shape)}")
+        n, m = int(C.shape[0]), int(C.shape[1])
+        like = C
+    if n < 1 or m < 1:
+        raise ParameterError(f"the cost matrix is empty: shape {(n, m)}")
+
+    # (the reference compares the concatenated table, so this practically never fires; kept where it is)
+    if np.array_equal(step_sizes_sigma, np.array([[1, 1]])) and n > m:
+        raise ParameterError("For diagonal matching: Y.shape[-1] >= X.shape[-11] (C.shape[1] >= C.shape[0])")
+
+    band = None
+    if global_constraints:
+        # util.fill_off_diagonal's rule (util/utils.py:2050-2067), applied as a predicate where C is read
+        radius = int(np.round(band_rad * min(n, m)))
+        offset = abs(n - m)
+        band = (-radius, radius + offset) if n < m else (-radius - offset, radius)
+
+    sess = _arrays.Session(like)
+    try:
+        ctx = sess.ctx
+        work = sess.scratch(16)
+        if C is None:
+            real = np.dtype(np.float32) if all(np.dtype(_arrays.numpy_dtype_of(a)) == np.float32 for a in (X, Y)) else np.dtype(np.float64)
+            x_ptr = sess.input_raw(_same_kind(sess, X), real)
+            y_ptr = sess.input_raw(_same_kind(sess, Y), real)
+            c_ptr = sess.scratch(8 * n * m)
+            flags = ctx.dtw_cost_exec(x_ptr, y_ptr, real, int(X.shape[0]), n, m, ctx.DTW_METRICS[metric], c_ptr, work)
+        else:
+            np_dtype = np.dtype(_arrays.numpy_dtype_of(C))
+            if np_dtype.name not in ctx.DTW_TYPES:
+                if np_dtype.kind not in "biuf":
+                    raise ParameterError(f"C must be real-valued, given dtype={np_dtype}")
+                C, np_dtype = _arrays.cast(C, np.float64), np.dtype(np.float64)
+            in_ptr = sess.input_raw(C, np_dtype)
+            c_ptr = in_ptr if np_dtype == np.float64 else sess.scratch(8 * n * m)   # (a float64 C is read where it lies)
+            flags = ctx.dtw_prepare_exec(in_ptr, np_dtype, n * m, 0 if np_dtype == np.float64 else c_ptr, work)
+        if flags & ctx.DTW_FLAG_NAN:
+            raise ParameterError("DTW cost matrix C has NaN values. ")
+
+        d_ptr, d_h = sess.output((n, m), np.float64)
+        idx_ptr = sess.scratch(n * m)
+        ctx.dtw_accumulate_exec(c_ptr, n, m, steps_table, weights_add, weights_mul, subseq, band, DTW_TILE, d_ptr, idx_ptr)
+
+        wp = None
+        if backtrack:
+            path_ptr, path_h = sess.output((n + m - 1, 2), np.int64)
+            length, status = ctx.dtw_backtrack_exec(d_ptr, idx_ptr, False, n, m, steps_table, subseq, ctx.DTW_START_ARGMIN if subseq else ctx.DTW_START_END, path_ptr, work)
+            if status & (ctx.DTW_FLAG_ROW_INF | ctx.DTW_FLAG_END_INF):
+                raise ParameterError(_NO_PATH_TEXT)
+            if status & ctx.DTW_FLAG_NOT_ORIGIN:
+                raise ParameterError("Unable to compute a full DTW warping path. You may want to try again with subseq=True.")
+            wp = sess.result(path_h)[:length]
+            # the reference's three conditions for flipping the pairs back (:480-485): X longer than Y, or a given C with more rows than columns
+            if subseq and (c_is_transposed or n > m):
+                wp = wp.flip(1) if sess.is_torch else np.fliplr(wp)
+        steps = None
+        if return_steps:
+            steps_ptr, steps_h = sess.output((n, m), np.int32)
+            ctx.dtw_widen_exec(idx_ptr, n * m, steps_ptr)
+            steps = sess.result(steps_h)
+        out = [sess.result(d_h)] + ([wp] if backtrack else []) + ([steps] if return_steps else [])
+        return tuple(out) if len(out) > 1 else out[0]
+    finally:
+        sess.close()
+
+
+def dtw_backtracking(steps, *, step_sizes_sigma=None, subseq=False, start=None):
+    """Backtrack a warping path from a step matrix (``librosa/sequence.py:643-694``), on the device: ``wp`` int64 (L, 2), a tensor where ``steps``
+    is one.  An index of ``steps`` outside the step table raises ``ParameterError`` (the reference: ``IndexError``)."""
+    if subseq is False and start is not None:
+        raise ParameterError(f"start is only allowed to be set if subseq is True (start={start}, subseq={subseq})")
+    default_steps = _dtw_default_steps()
+    if step_sizes_sigma is None:
+        step_sizes_sigma = default_steps
+    else:
+        step_sizes_sigma = np.concatenate((default_steps, _host(step_sizes_sigma)))
+    if np.any(step_sizes_sigma < 0):
+        raise ParameterError("step_sizes_sigma cannot contain negative values")
+    steps_table = _dtw_device_limits(step_sizes_sigma)
+    if steps.ndim != 2 or int(steps.shape[0]) < 1 or int(steps.shape[1]) < 1:
+        raise ParameterError(f"steps must be a non-empty matrix, given shape {tuple(steps.shape)}")
+    n, m = int(steps.shape[0]), int(steps.shape[1])
+    if start is not None and not 0 <= int(start) < m:
+        raise ParameterError(f"start={start} is not a column of steps (shape {(n, m)})")
+    sess = _arrays.Session(steps)
+    try:
+        ctx = sess.ctx
+        idx_ptr = sess.input_raw(steps, np.int32)
+        path_ptr, path_h = sess.output((n + m - 1, 2), np.int64)
+        length, status = ctx.dtw_backtrack_exec(0, idx_ptr, True, n, m, steps_table, subseq, ctx.DTW_START_END if start is None else int(start), path_ptr, sess.scratch(16))
+        if status & ctx.DTW_FLAG_BAD_STEP:
+            raise ParameterError(f"steps holds an index outside the step table of {len(steps_table)} steps")
+        return sess.result(path_h)[:length]
+    finally:
+        sess.close()
