@@ -498,6 +498,24 @@ int lra_dtw_widen_exec(lra_ctx* ctx, const void* step_idx, int64_t count, void* 
 int lra_dtw_backtrack_exec(lra_ctx* ctx, const void* D, const void* step_idx, int steps_i32, int64_t N, int64_t M, const int32_t* steps, int n_steps, int subseq, int64_t start, void* path,
                            void* work, int64_t* length, int* status);
 
+/* ---- sequence.rqa: librosa/sequence.py:698-1074 --------------------------------------------------------------------------------------------- */
+#define LRA_RQA_WORK_BYTES (16 + 16 * 1024) /* the work area of lra_rqa_argmax_exec and lra_rqa_backtrack_exec (device) */
+/* Bytes of LDS a workgroup of lra_rqa_score_exec needs (host arithmetic only) for blocks of `rows` rows and strips of `strip` columns (0: the
+ * library's choice): three rows of strip + 2 (rows - 1) + 2 pairs of float64.  0 for a geometry that is not served: rows is a
+ * power of two up to 64, strip a power of two from 4 to 1024. */
+int64_t lra_rqa_lds_bytes(int rows, int strip);
+/* __rqa_dp (:869-1023) of sim [N][M] of `dtype` (LRA_F32 or LRA_F64; device, never written): score [N][M] of the same type and the pointers int8
+ * [N][M] (device): 0 diagonal, 1 the left knight (-1, -2), 2 the up knight (-2, -1), -1 a reset outside the path, -2 the start of a sequence.
+ * Candidates are formed in float64, each operation rounded on its own, and the score is rounded once to `dtype` by the store; np.argmax's order
+ * (the first maximum, a NaN first).  One launch per block of `rows` rows, in stream order; the result does not depend on (rows, strip). */
+int lra_rqa_score_exec(lra_ctx* ctx, const void* sim, int dtype, int64_t N, int64_t M, double gap_onset, double gap_extend, int knight_moves, int rows, int strip, void* score,
+                       void* pointers);
+/* np.argmax(score) over `count` elements of `dtype` (device): the flat index goes to the first 8 bytes of work (LRA_RQA_WORK_BYTES, device). */
+int lra_rqa_argmax_exec(lra_ctx* ctx, const void* score, int dtype, int64_t count, void* work);
+/* __rqa_backtrack (:1026-1074) over the pointers of lra_rqa_score_exec from the cell lra_rqa_argmax_exec left in work: the path in ascending
+ * order in the LAST *length rows of path, uint64 [min(N, M)][2] (device) (this waits for the stream). */
+int lra_rqa_backtrack_exec(lra_ctx* ctx, const void* pointers, int64_t N, int64_t M, void* work, void* path, int64_t* length);
+
 /* ---- the back half of pyin around the decode: librosa.pyin, librosa/core/pitch.py:796-852 and __pyin_helper :855-931 ---------------------- */
 #define LRA_PYIN_LDS_MAX (160 * 1024)
 /* Bytes of LDS a workgroup of lra_pyin_obs_exec needs (host arithmetic only): per frame the voiced row (8 n_pitch_bins) and two counters per

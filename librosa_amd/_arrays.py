@@ -31,7 +31,7 @@ def _torch():
     if not _NP2TORCH:
         _NP2TORCH.update({np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
                           np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128,
-                          np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16})   # integers: index tables (CSR bases), integer-valued inputs and state paths (uint16)
+                          np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16, np.dtype(np.uint64): torch.uint64})   # integers: index tables (CSR bases), integer-valued inputs, state paths (uint16) and alignment paths (uint64)
     return torch
 
 

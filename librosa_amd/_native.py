@@ -130,6 +130,10 @@ SIGNATURES = {
     "lra_dtw_accumulate_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "lra_dtw_widen_exec": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "lra_dtw_backtrack_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int)]),
+    "lra_rqa_lds_bytes": (c_int64, [c_int, c_int]),
+    "lra_rqa_score_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "lra_rqa_argmax_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "lra_rqa_backtrack_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -713,6 +717,23 @@ class Context:
         _check(self.lib.lra_dtw_backtrack_exec(self.handle, c_void_p(d_ptr or None), c_void_p(step_idx_ptr), int(bool(steps_i32)), int(n), int(m), c_void_p(steps.ctypes.data),
                                                int(steps.shape[0]), int(bool(subseq)), int(start), c_void_p(path_ptr), c_void_p(work_ptr), byref(length), byref(status)))
         return int(length.value), int(status.value)
+
+    RQA_WORK_BYTES = 16 + 16 * 1024   # LRA_RQA_WORK_BYTES
+
+    def rqa_score_exec(self, sim_ptr, dtype, n, m, gap_onset, gap_extend, knight_moves, rows, strip, score_ptr, pointers_ptr):
+        """The alignment score matrix (of ``dtype``) and the int8 pointers (``include/librosa_amd.h``: lra_rqa_score_exec)."""
+        _check(self.lib.lra_rqa_score_exec(self.handle, c_void_p(sim_ptr), dtype_code(dtype), int(n), int(m), float(gap_onset), float(gap_extend), int(bool(knight_moves)), int(rows),
+                                           int(strip), c_void_p(score_ptr), c_void_p(pointers_ptr)))
+
+    def rqa_argmax_exec(self, score_ptr, dtype, count, work_ptr):
+        """np.argmax(score) into the work area (lra_rqa_argmax_exec)."""
+        _check(self.lib.lra_rqa_argmax_exec(self.handle, c_void_p(score_ptr), dtype_code(dtype), int(count), c_void_p(work_ptr)))
+
+    def rqa_backtrack_exec(self, pointers_ptr, n, m, work_ptr, path_ptr):
+        """The alignment path into the last rows of ``path`` (lra_rqa_backtrack_exec).  Returns its length (this waits for the stream)."""
+        length = c_int64(0)
+        _check(self.lib.lra_rqa_backtrack_exec(self.handle, c_void_p(pointers_ptr), int(n), int(m), c_void_p(work_ptr), c_void_p(path_ptr), byref(length)))
+        return int(length.value)
 
     VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
     VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits

@@ -22,6 +22,18 @@ else raises ``ParameterError``: there is no CPU fallback); the features of ``X``
 ``(0, 0)`` is refused; at most ``DTW_MAX_STEPS`` = 16 steps with the three defaults and no step component above ``DTW_MAX_STEP`` = 8;
 ``dtw_backtracking`` on a ``steps`` matrix holding an index outside the step table, or with ``start`` outside the columns, raises
 ``ParameterError`` where the reference raises ``IndexError``.
+
+``rqa`` (``librosa/sequence.py:698-1074``) has the reference's signature, check order, texts and return shapes.  The score matrix and the pointers
+(``rqa_score``: blocks of ``RQA_ROWS`` rows, one launch per block, one workgroup per strip of ``RQA_STRIP`` columns that recomputes its left
+halo), ``np.argmax(score)`` (``rqa_argmax``) and the walk (``rqa_backtrack``) are computed on the device (``csrc/lra_rqa.h``).  float32 and
+float64 ``sim`` are scored in their own type and ``score`` is the reference's bit for bit; ``path`` is uint64.
+
+Differences from the reference for RQA: the walk follows the move that was scored -- the device stores its own pointer codes
+(0 diagonal, 1 left knight ``(-1, -2)``, 2 up knight ``(-2, -1)``, -1 and -2 as the reference), where the reference numbers the up knight 1 in
+column 1, reads it back as the left knight and steps to column -1 (its path is then cut short, or holds ``2**64 - 1``); wherever the
+reference's walk stays inside the matrix the two paths agree.  bool and integer ``sim`` of any width are widened to float64 and ``score`` comes
+back as float64, equal to the reference's result on ``sim.astype(float64)`` (the reference truncates the score into the integer type).  Complex or
+non-numeric ``sim``, ``sim.ndim != 2`` and an empty ``sim`` raise ``ParameterError`` (the reference: ``IndexError`` for an empty one).
 """
 from __future__ import annotations
 
@@ -32,7 +44,7 @@ from .filters import get_window
 from .util.exceptions import ParameterError
 from .util.utils import is_positive_int, is_torch_tensor, pad_center, tiny
 
-__all__ = ["dtw", "dtw_backtracking", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local"]
+__all__ = ["dtw", "dtw_backtracking", "rqa", "viterbi", "viterbi_discriminative", "viterbi_binary", "transition_uniform", "transition_loop", "transition_cycle", "transition_local"]
 
 MAX_STATES = 8192            # LRA_VITERBI_MAX_STATES
 _SMALL_MAX = 32              # LRA_VITERBI_SMALL_MAX: up to here the threshold is a comparison in the kernel, beyond it a list
@@ -618,5 +630,68 @@ def dtw_backtracking(steps, *, step_sizes_sigma=None, subseq=False, start=None):
         if status & ctx.DTW_FLAG_BAD_STEP:
             raise ParameterError(f"steps holds an index outside the step table of {len(steps_table)} steps")
         return sess.result(path_h)[:length]
+    finally:
+        sess.close()
+
+
+# ---- recurrence quantification analysis (librosa/sequence.py:698-1074) --------------------------------------------------------------------------
+RQA_ROWS = 0                 # the scoring kernel's rows per launch: 0 for the library's choice, or a power of two up to 64
+RQA_STRIP = 0                # its columns per workgroup: 0 for the library's choice, or a power of two from 4 to 1024 (tests reach many launches and strips at tiny shapes)
+
+
+def rqa(sim, *, gap_onset=1, gap_extend=1, knight_moves=True, backtrack=True):
+    """Recurrence quantification analysis (``librosa/sequence.py:698-1074``): the alignment score matrix ``score`` of a self- or cross-similarity
+    matrix ``sim`` (N, M), in ``sim``'s type for float32 and float64 (float64 for bool and integer ``sim``), and with ``backtrack`` the best
+    alignment ``path`` (uint64, (k, 2), ascending; (0, 2) where nothing aligns), all computed on the device.  NumPy input gives NumPy results, a
+    tensor on the device gives tensors there; the input is never written.  Differences from the reference: the module docstring."""
+    if gap_onset < 0:
+        raise ParameterError("gap_onset={} must be strictly positive")
+    if gap_extend < 0:
+        raise ParameterError("gap_extend={} must be strictly positive")
+    if not (is_torch_tensor(sim) or isinstance(sim, np.ndarray)):
+        sim = np.asarray(sim)
+    if sim.ndim != 2:
+        raise ParameterError(f"sim must be a matrix, given shape {tuple(sim.shape)}")
+    n, m = int(sim.shape[0]), int(sim.shape[1])
+    if n < 1 or m < 1:
+        raise ParameterError(f"sim is empty: shape {(n, m)}")
+    if is_torch_tensor(sim):
+        import torch
+
+        if sim.dtype == torch.bool:
+            sim = sim.view(torch.uint8)
+        elif sim.is_complex():
+            raise ParameterError(f"sim must be real-valued, given dtype={sim.dtype}")
+    elif sim.dtype == np.bool_:
+        sim = sim.view(np.uint8)
+    np_dtype = np.dtype(_arrays.numpy_dtype_of(sim))
+    if np_dtype.kind not in "iuf":
+        raise ParameterError(f"sim must be real-valued, given dtype={np_dtype}")
+    widen = np_dtype.name in ("uint8", "int32", "int64")   # (exactly, on the device: dtw_prepare)
+    if np_dtype not in (np.dtype(np.float32), np.dtype(np.float64)) and not widen:
+        sim, np_dtype = _arrays.cast(sim, np.float64), np.dtype(np.float64)
+    real = np.dtype(np.float64) if widen else np_dtype
+
+    sess = _arrays.Session(sim)
+    try:
+        ctx = sess.ctx
+        sim_ptr = sess.input_raw(sim, np_dtype)
+        if widen:
+            in_ptr, sim_ptr = sim_ptr, sess.scratch(8 * n * m)
+            ctx.dtw_prepare_exec(in_ptr, np_dtype, n * m, sim_ptr, sess.scratch(16))   # (its NaN flag: an integer holds none)
+        score_ptr, score_h = sess.output((n, m), real)
+        ptr_ptr = sess.scratch(n * m)
+        ctx.rqa_score_exec(sim_ptr, real, n, m, gap_onset, gap_extend, knight_moves, RQA_ROWS, RQA_STRIP, score_ptr, ptr_ptr)
+        if not backtrack:
+            return sess.result(score_h)
+        cap = min(n, m)
+        # (allocated as int64 and viewed as uint64: not every torch build slices or copies uint64 on the device)
+        path_ptr, path_h = sess.output((cap, 2), np.int64)
+        work = sess.scratch(ctx.RQA_WORK_BYTES)
+        ctx.rqa_argmax_exec(score_ptr, real, n * m, work)
+        length = ctx.rqa_backtrack_exec(ptr_ptr, n, m, work, path_ptr)
+        path = sess.result(path_h)[cap - length:]
+        path = path.view(_arrays.torch_dtype(np.uint64)) if sess.is_torch else path.view(np.uint64)
+        return sess.result(score_h), path
     finally:
         sess.close()
