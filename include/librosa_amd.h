@@ -516,6 +516,55 @@ int lra_rqa_argmax_exec(lra_ctx* ctx, const void* score, int dtype, int64_t coun
  * order in the LAST *length rows of path, uint64 [min(N, M)][2] (device) (this waits for the stream). */
 int lra_rqa_backtrack_exec(lra_ctx* ctx, const void* pointers, int64_t N, int64_t M, void* work, void* path, int64_t* length);
 
+/* ---- segment.cross_similarity and recurrence_matrix: librosa/segment.py:67-357, :361-706, __affinity_bandwidth :1332-1437 ------------------- */
+#define LRA_KNN_MAX_K 2048     /* the longest neighbour list a query frame keeps */
+#define LRA_KNN_WORK_BYTES 64  /* the work area of the calls below (device) */
+#define LRA_KNN_CONNECTIVITY 0
+#define LRA_KNN_DISTANCE 1
+#define LRA_KNN_AFFINITY 2
+#define LRA_KNN_BW_SCALAR 0 /* a given scalar, or np.nanmedian of the rows' distance to the bandwidth_k-th neighbour left in the work area */
+#define LRA_KNN_BW_MEAN_K 1
+#define LRA_KNN_BW_GMEAN_K 2
+#define LRA_KNN_BW_MEAN_K_AVG 3
+#define LRA_KNN_BW_GMEAN_K_AVG 4
+#define LRA_KNN_BW_MEAN_K_AVG_AND_PAIR 5
+#define LRA_KNN_BW_MATRIX 6 /* a float64 matrix [n][m], gathered at the stored entries */
+#define LRA_KNN_STATUS_EMPTY_GRAPH 1  /* no row has a finite distance to its bandwidth_k-th neighbour */
+#define LRA_KNN_STATUS_ROW_EMPTY 2    /* a row stores no entry */
+#define LRA_KNN_STATUS_NON_POSITIVE 4 /* an entry of the bandwidth matrix is <= 0 */
+/* Bytes of LDS a workgroup of lra_knn_select_exec needs (host arithmetic only) for `rows` query frames per workgroup, candidate tiles of
+ * `tile` frames (0: the library's choice) and lists of k pairs.  0 for a geometry that is not served: rows is a power of two up to 16, tile a
+ * power of two from 4 to 1024, rows * tile <= 2048, k <= LRA_KNN_MAX_K, and everything fits 64 KiB. */
+int64_t lra_knn_lds_bytes(int rows, int tile, int k);
+/* The k nearest candidates of every query frame: Q [n_features][n] and R [n_features][m] of `dtype` (LRA_F32 or LRA_F64; device, never written),
+ * `metric` one of LRA_DTW_EUCLIDEAN ... LRA_DTW_COSINE, summed over the features in ascending order in float64, every operation rounded on its own.  The candidates of frame i are the j with
+ * |i - j| >= width (width 0: all) and, with skip_zero, a distance that is not exactly 0; pairs are ordered by distance, ties by the lower index, a
+ * NaN last.  count int32 [n], index int32 [n][k] ascending in each row, distance float64 [n][k] (device).  No buffer of n * m elements is used;
+ * the result does not depend on (rows, tile). */
+int lra_knn_select_exec(lra_ctx* ctx, const void* Q, const void* R, int dtype, int64_t n_features, int64_t n, int64_t m, int metric, int k, int64_t width, int skip_zero, int rows, int tile,
+                        void* count, void* index, void* distance);
+/* keep uint8 [n][k] (device): an entry stays unless drop_zero and its distance is exactly 0, or sym and frame i is not in the list of frame j. */
+int lra_knn_mutual_exec(lra_ctx* ctx, int64_t n, int k, const void* count, const void* index, const void* distance, int sym, int drop_zero, void* keep);
+/* Per row, over the kept distances (keep null: all) and, with add_self, a 0 for the self link: dist_to_k, the min(bandwidth_k, stored)-th smallest,
+ * and avg, the mean of those first ones (float64 [n], device; NaN for an empty row).  With `median`, np.nanmedian(dist_to_k) is left in the work
+ * area for LRA_KNN_BW_SCALAR.  *status: LRA_KNN_STATUS_* bits; *first_empty: the lowest empty row (this waits for the stream). */
+int lra_knn_bandwidth_exec(lra_ctx* ctx, int64_t n, int k, const void* count, const void* distance, const void* keep, int add_self, int bandwidth_k, int median, void* dist_to_k, void* avg,
+                           void* work, int* status, int64_t* first_empty);
+/* (matrix <= 0).any() of a float64 bandwidth matrix (device) -> LRA_KNN_STATUS_NON_POSITIVE in *status (this waits for the stream). */
+int lra_knn_bw_check_exec(lra_ctx* ctx, const void* matrix, int64_t count, void* work, int* status);
+/* The result of the lists: entry (i, j) holds 1 (uint8, LRA_KNN_CONNECTIVITY), the distance, or exp(distance / -bandwidth) (float64), and with
+ * `self` the link (i, i) at distance 0 is stored too.  Either the transposed dense result `dense` [m][n] (zero elsewhere), or, dense null, the
+ * compressed arrays: indptr int32 [n + 1], indices int32 and data [*total] in ascending order per row, counts int32 [n] scratch (device;
+ * this waits for the stream).  bw_on_device: LRA_KNN_BW_SCALAR reads lra_knn_bandwidth_exec's median from the work area instead of bw_scalar;
+ * sigma: dist_to_k or avg, as bw_mode asks; matrix: LRA_KNN_BW_MATRIX's. */
+int lra_knn_emit_exec(lra_ctx* ctx, int64_t n, int64_t m, int k, const void* count, const void* index, const void* distance, const void* keep, int self, int mode, int bw_mode,
+                      double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, void* work, void* counts, void* indptr, void* indices, void* data, void* dense,
+                      int64_t* total);
+/* The same result where every candidate is kept, straight from the distances: out [m][n] (device) with out[j][i] the value of entry (i, j) for
+ * |i - j| >= width (and, but for connectivity, a distance that is not exactly 0), the self link as above, 0 elsewhere. */
+int lra_knn_dense_exec(lra_ctx* ctx, const void* Q, const void* R, int dtype, int64_t n_features, int64_t n, int64_t m, int metric, int64_t width, int self, int mode, int bw_mode,
+                       double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, void* work, void* out);
+
 /* ---- the back half of pyin around the decode: librosa.pyin, librosa/core/pitch.py:796-852 and __pyin_helper :855-931 ---------------------- */
 #define LRA_PYIN_LDS_MAX (160 * 1024)
 /* Bytes of LDS a workgroup of lra_pyin_obs_exec needs (host arithmetic only): per frame the voiced row (8 n_pitch_bins) and two counters per

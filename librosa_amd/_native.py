@@ -134,6 +134,14 @@ SIGNATURES = {
     "lra_rqa_score_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lra_rqa_argmax_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p]),
     "lra_rqa_backtrack_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "lra_knn_lds_bytes": (c_int64, [c_int, c_int, c_int]),
+    "lra_knn_select_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "lra_knn_mutual_exec": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lra_knn_bandwidth_exec": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int64)]),
+    "lra_knn_bw_check_exec": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int)]),
+    "lra_knn_emit_exec": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "lra_knn_dense_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -734,6 +742,51 @@ class Context:
         length = c_int64(0)
         _check(self.lib.lra_rqa_backtrack_exec(self.handle, c_void_p(pointers_ptr), int(n), int(m), c_void_p(work_ptr), c_void_p(path_ptr), byref(length)))
         return int(length.value)
+
+    KNN_MAX_K, KNN_WORK_BYTES = 2048, 64   # LRA_KNN_MAX_K, LRA_KNN_WORK_BYTES
+    KNN_MODES = {"connectivity": 0, "distance": 1, "affinity": 2}   # the LRA_KNN_* modes
+    KNN_BW_SCALAR, KNN_BW_MATRIX = 0, 6
+    KNN_BW_MODES = {"med_k_scalar": 0, "mean_k": 1, "gmean_k": 2, "mean_k_avg": 3, "gmean_k_avg": 4, "mean_k_avg_and_pair": 5}   # the LRA_KNN_BW_* modes
+    KNN_STATUS_EMPTY_GRAPH, KNN_STATUS_ROW_EMPTY, KNN_STATUS_NON_POSITIVE = 1, 2, 4   # the LRA_KNN_STATUS_* bits
+
+    def knn_select_exec(self, q_ptr, r_ptr, dtype, n_features, n, m, metric, k, width, skip_zero, rows, tile, count_ptr, index_ptr, distance_ptr):
+        """The k nearest candidates of every query frame, each row sorted by index (``include/librosa_amd.h``: lra_knn_select_exec)."""
+        _check(self.lib.lra_knn_select_exec(self.handle, c_void_p(q_ptr), c_void_p(r_ptr), dtype_code(dtype), int(n_features), int(n), int(m), int(metric), int(k), int(width),
+                                            int(bool(skip_zero)), int(rows), int(tile), c_void_p(count_ptr), c_void_p(index_ptr), c_void_p(distance_ptr)))
+
+    def knn_mutual_exec(self, n, k, count_ptr, index_ptr, distance_ptr, sym, drop_zero, keep_ptr):
+        """Which list entries stay (lra_knn_mutual_exec)."""
+        _check(self.lib.lra_knn_mutual_exec(self.handle, int(n), int(k), c_void_p(count_ptr), c_void_p(index_ptr), c_void_p(distance_ptr), int(bool(sym)), int(bool(drop_zero)),
+                                            c_void_p(keep_ptr)))
+
+    def knn_bandwidth_exec(self, n, k, count_ptr, distance_ptr, keep_ptr, add_self, bandwidth_k, median, dist_to_k_ptr, avg_ptr, work_ptr):
+        """The rows' bandwidth statistics and, with ``median``, their nanmedian into the work area (lra_knn_bandwidth_exec).  Returns (status bits,
+        the lowest empty row) (this waits for the stream)."""
+        status, first = c_int(0), c_int64(0)
+        _check(self.lib.lra_knn_bandwidth_exec(self.handle, int(n), int(k), c_void_p(count_ptr), c_void_p(distance_ptr), c_void_p(keep_ptr), int(bool(add_self)), int(bandwidth_k),
+                                               int(bool(median)), c_void_p(dist_to_k_ptr), c_void_p(avg_ptr), c_void_p(work_ptr), byref(status), byref(first)))
+        return int(status.value), int(first.value)
+
+    def knn_bw_check_exec(self, matrix_ptr, count, work_ptr):
+        """The status bits of a bandwidth matrix (lra_knn_bw_check_exec; this waits for the stream)."""
+        status = c_int(0)
+        _check(self.lib.lra_knn_bw_check_exec(self.handle, c_void_p(matrix_ptr), int(count), c_void_p(work_ptr), byref(status)))
+        return int(status.value)
+
+    def knn_emit_exec(self, n, m, k, count_ptr, index_ptr, distance_ptr, keep_ptr, self_link, mode, bw_mode, bw_scalar, bw_on_device, sigma_ptr, matrix_ptr, work_ptr, counts_ptr, indptr_ptr,
+                      indices_ptr, data_ptr, dense_ptr):
+        """The dense result, or the compressed arrays, of the lists (lra_knn_emit_exec).  Returns the number of stored entries of the compressed
+        arrays (this waits for the stream), 0 for a dense result."""
+        total = c_int64(0)
+        _check(self.lib.lra_knn_emit_exec(self.handle, int(n), int(m), int(k), c_void_p(count_ptr), c_void_p(index_ptr), c_void_p(distance_ptr), c_void_p(keep_ptr), int(bool(self_link)),
+                                          int(mode), int(bw_mode), float(bw_scalar), int(bool(bw_on_device)), c_void_p(sigma_ptr), c_void_p(matrix_ptr), c_void_p(work_ptr),
+                                          c_void_p(counts_ptr), c_void_p(indptr_ptr), c_void_p(indices_ptr), c_void_p(data_ptr), c_void_p(dense_ptr), byref(total)))
+        return int(total.value)
+
+    def knn_dense_exec(self, q_ptr, r_ptr, dtype, n_features, n, m, metric, width, self_link, mode, bw_mode, bw_scalar, bw_on_device, sigma_ptr, matrix_ptr, work_ptr, out_ptr):
+        """The transposed dense result where every candidate is kept (lra_knn_dense_exec)."""
+        _check(self.lib.lra_knn_dense_exec(self.handle, c_void_p(q_ptr), c_void_p(r_ptr), dtype_code(dtype), int(n_features), int(n), int(m), int(metric), int(width), int(bool(self_link)),
+                                           int(mode), int(bw_mode), float(bw_scalar), int(bool(bw_on_device)), c_void_p(sigma_ptr), c_void_p(matrix_ptr), c_void_p(work_ptr), c_void_p(out_ptr)))
 
     VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
     VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits

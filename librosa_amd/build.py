@@ -4,7 +4,7 @@ The library holds several hundred instances of the fused kernels; hipcc compiles
 one core, so the instances are split into groups (``csrc/lra_fused.h``) that are compiled side by side:
 ``lra_inst.hip`` once per group plus the units of ``UNITS`` below -- ``lra_api.hip`` (host API, general rocFFT path) and one
 ``lra_<feature>_inst.hip`` per family of kernels with a translation unit of its own (mixed-radix transforms, tempogram, beat
-tracker, peak picker, chroma, pitch tracker and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA) -- then one link.  The
+tracker, peak picker, chroma, pitch tracker and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA, neighbour graphs) -- then one link.  The
 result ``librosa_amd/_liblibrosa_amd.so`` is git-ignored but travels to the GPU box with the repo snapshot.
 hipcc cross-compiles for gfx950 without a GPU.
 """
@@ -25,7 +25,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # the translation units csrc/lra_<unit>.hip that are compiled once each (lra_inst.hip is compiled once per instance group besides);
 # scripts/device_asm_diff.sh reads this list
-UNITS = ("api", "mixed_inst", "rhythm_inst", "beat_inst", "peaks_inst", "chroma_inst", "pitch_inst", "yin_inst", "viterbi_inst", "pyin_inst", "dtw_inst", "rqa_inst")
+UNITS = ("api", "mixed_inst", "rhythm_inst", "beat_inst", "peaks_inst", "chroma_inst", "pitch_inst", "yin_inst", "viterbi_inst", "pyin_inst", "dtw_inst", "rqa_inst", "knn_inst")
 
 
 def sources():

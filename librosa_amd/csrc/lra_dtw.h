@@ -175,6 +175,38 @@ __device__ __forceinline__ double dtw_feature(const void* p, int f64, long long 
     return f64 ? reinterpret_cast<const double*>(p)[at] : (double)reinterpret_cast<const float*>(p)[at];
 }
 
+// The metric body, shared with the neighbour search (lra_knn.h): one feature (x, y) added to the running sums in ascending feature order, every
+// product and sum rounded on its own (contraction off), so that the sums are those of a NumPy model bit for bit.  cost_body below keeps its own
+// statements: the compiler contracts some of them into fused multiply-adds, its results have shipped with those bits, and routing it through
+// this function changes them ...
+__device__ __forceinline__ void dtw_metric_add(int metric, double x, double y, double& acc, double& xx, double& yy) {
+#pragma clang fp contract(off)
+    if (metric == kCosine) {
+        acc += x * y;
+        xx += x * x;
+        yy += y * y;
+    } else if (metric == kCityblock) {
+        acc += __builtin_fabs(x - y);
+    } else {
+        const double d = x - y;
+        acc += d * d;
+    }
+}
+
+// ... and the distance of the finished sums (cost_body's too: nothing here can be contracted)
+__device__ __forceinline__ double dtw_metric_finish(int metric, double acc, double xx, double yy) {
+    double c = acc;
+    if (metric == kEuclidean) {
+        c = sqrt(c);
+    } else if (metric == kCosine) {
+        // scipy's cdist: the cosine clipped to [-1, 1], then 1 - cosine; 0 / 0 is NaN and stays NaN
+        double cs = acc / (sqrt(xx) * sqrt(yy));
+        if (__builtin_fabs(cs) > 1.0) cs = cs < 0.0 ? -1.0 : 1.0;
+        c = 1.0 - cs;
+    }
+    return c;
+}
+
 // grid = ceil(N / kCostTile) * ceil(M / kCostTile) workgroups of kCostNT threads; thread (ty, tx) forms C[n0 + ty + 8 i][m0 + tx], i < 4
 __device__ __forceinline__ void cost_body(const CostArgs& a) {
     __shared__ double xs[kCostK][kCostTile];
@@ -218,15 +250,7 @@ __device__ __forceinline__ void cost_body(const CostArgs& a) {
     for (int i = 0; i < kPer; ++i) {
         const long long n = n0 + ty + kRows * i, m = m0 + tx;
         if (n >= a.N || m >= a.M) continue;
-        double c = acc[i];
-        if (a.metric == kEuclidean) {
-            c = sqrt(c);
-        } else if (a.metric == kCosine) {
-            // scipy's cdist: the cosine clipped to [-1, 1], then 1 - cosine; 0 / 0 is NaN and stays NaN
-            double cs = acc[i] / (sqrt(xx[i]) * sqrt(yy[i]));
-            if (__builtin_fabs(cs) > 1.0) cs = cs < 0.0 ? -1.0 : 1.0;
-            c = 1.0 - cs;
-        }
+        const double c = dtw_metric_finish(a.metric, acc[i], xx[i], yy[i]);
         if (c != c) flags |= kFlagNan;
         a.C[n * a.M + m] = c;
     }
