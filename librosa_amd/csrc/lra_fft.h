@@ -11,7 +11,7 @@
 // LDS layout of one frame: complex element i lives at slot phys(i) = i + (i >> logr(0)).  The
 // one-slot pad every r0 elements makes the first pass's stride-r0 stores conflict-free
 // (stride r0+1 slots = 2(r0+1) dwords: the 16 lanes of a ds_write_b64 group hit 16 distinct
-// even banks) while keeping the later unit-stride accesses essentially contiguous.
+// even banks) while keeping the later unit-stride accesses essentially contiguous (FftCfg::X1T / X2U: "exchange addresses" below).
 //
 // Reference semantics implemented by the callers (lra_kernels.h): librosa/core/spectrum.py:
 // 380-390 (rfft of windowed frames) and :598 (irfft of spectrogram columns).
@@ -77,6 +77,13 @@ template <int LOGM_, int LOGR_, class T_, int NTMIN_ = 256, int MINW_ = 0, bool 
     static constexpr int FRAME_ELEMS = M + (M >> PADSHIFT) + 1;
     static constexpr int FRAME_BYTES = ((FRAME_ELEMS * (int)sizeof(cplx) + 15) / 16) * 16;
     static constexpr int phys(int i) { return i + (i >> PADSHIFT); }
+    // LDS layout of the exchanges between passes (see "exchange addresses" below).  X1T: pass 0 -> pass 1 through the TRANSPOSED layout (output j of
+    // lane tf at unit tf + X1_PITCH j); X2U: pass 1 -> last pass through the UNPADDED layout (element i at unit i).  One wave per frame with a
+    // radix-16 first pass, float32, M = 1024: radices 16-8-8 take both, 16-16-4 the first (its middle -> last hand-over, v3_mid_write, is conflict-free
+    // already).  Every other configuration keeps phys() throughout.
+    static constexpr bool X1T = TF == 64 && R == 16 && M == 1024 && logr(0) == 4 && sizeof(T_) == 4;
+    static constexpr bool X2U = X1T && PLAN_ == 0 && P == 3;
+    static constexpr int X1_PITCH = 66;  // units per row of the transposed layout: sixteen rows 66 units apart put a 32-lane read group on 64 distinct banks
     static constexpr int MIN_WAVES = MINW_ > 0 ? MINW_ : 2;
     static constexpr bool HOIST = HOIST_;
     // same transform, different workgroup size (the mel kernel shares its filter tables across slots)
@@ -172,15 +179,65 @@ template <class T> struct Dft<2, T> {
 template <class Cfg> constexpr int pstride(int c) { return c + (c >> Cfg::PADSHIFT); }
 template <class Cfg> constexpr bool affine_tf() { return Cfg::TF % (1 << Cfg::PADSHIFT) == 0; }
 
+// ---- exchange addresses.  Every LDS access of the passes is "per-lane base + compile-time offset" (in units of one complex element); the four sites
+// -- pass-0 write, pass-1 read, pass-1 write, last-pass read -- are spelled here once, for the kernels and for the layout checker
+// (tests/lds_layout_check.cpp).  xw_*<p>: where pass p puts output j of its butterfly tf + i TF; xr_*<p>: where pass p finds input j of that butterfly.
+// Valid where the pass's affine form applies (xw_affine / xr_affine); the lane of a read may be any butterfly index below TF or, in the last pass, its mirror.
+//   exchange 1 (X1T): logical element 16 tw + k1 (output k1 of pass-0 lane tw) lives at unit tw + 66 k1.  Stores: sixteen consecutive lanes, sixteen
+//     consecutive units.  Reads: pass-1 lane l wants k1 = l & 15, tw = (l >> 4) + (i TF + j sin) / 16: unit 66 (l & 15) + (l >> 4) + const; over a 32-lane
+//     group the dwords 132 a + 2 h (+ 1), a < 16, h < 2, fall on 64 distinct banks (phys: the group straddles a pad unit, every read 2-way).
+//   exchange 2 (X2U): element i at unit i.  Stores: 16 consecutive units per lane group; reads: 32 consecutive units (butterfly tf), or units
+//     M/8 - tf descending with lane 0 at M/16 (the mirror): distinct modulo 32 either way.
+template <class Cfg, int p> constexpr bool xw_affine() {
+    constexpr int s = 1 << Cfg::logs(p);
+    return affine_tf<Cfg>() && (p == 0 || p == Cfg::P - 1 || Cfg::TF % s == 0);
+}
+template <class Cfg, int p> constexpr bool xr_affine() { return affine_tf<Cfg>() && (Cfg::M >> Cfg::logr(p)) % (1 << Cfg::PADSHIFT) == 0; }
+// 0: phys(), 1: transposed (exchange 1), 2: unpadded (exchange 2)
+template <class Cfg, int p> constexpr int xw_layout() { return p == 0 && Cfg::X1T ? 1 : (p == 1 && Cfg::X2U ? 2 : 0); }
+template <class Cfg, int p> constexpr int xr_layout() { return p == 1 && Cfg::X1T ? 1 : (p == 2 && Cfg::X2U ? 2 : 0); }
+
+template <class Cfg, int p> LRA_HD constexpr int xw_base(int tf) {
+    constexpr int lr = Cfg::logr(p), r = 1 << lr, s = 1 << Cfg::logs(p);
+    if constexpr (p == 0) return xw_layout<Cfg, p>() == 1 ? tf : tf * (r + 1);  // s = 1, k = 0: position b r + j with b r a multiple of Q = r: phys = b (r + 1) + j
+    else if constexpr (p == Cfg::P - 1) return Cfg::phys(tf);                     // b < s, so k = b and the output position is tf + i TF + j s
+    else {
+        const int k = tf & (s - 1);  // TF % s == 0: k does not depend on i
+        const int e = ((tf - k) << lr) + k;
+        return xw_layout<Cfg, p>() == 2 ? e : Cfg::phys(e);
+    }
+}
+template <class Cfg, int p> constexpr int xw_off(int i, int j) {
+    constexpr int lr = Cfg::logr(p), r = 1 << lr, s = 1 << Cfg::logs(p);
+    if (p == 0) return xw_layout<Cfg, p>() == 1 ? Cfg::X1_PITCH * j : i * Cfg::TF * (r + 1) + j;  // (transposed: one butterfly per lane, i = 0)
+    if (p == Cfg::P - 1) return i * pstride<Cfg>(Cfg::TF) + j * pstride<Cfg>(s);
+    return xw_layout<Cfg, p>() == 2 ? i * (Cfg::TF << lr) + j * s : i * pstride<Cfg>(Cfg::TF << lr) + j * pstride<Cfg>(s);
+}
+template <class Cfg, int p> LRA_HD constexpr int xr_base(int b) {
+    if constexpr (xr_layout<Cfg, p>() == 1) return Cfg::X1_PITCH * (b & 15) + (b >> 4);
+    else if constexpr (xr_layout<Cfg, p>() == 2) return b;
+    else return Cfg::phys(b);
+}
+template <class Cfg, int p> constexpr int xr_off(int i, int j) {
+    constexpr int sin = Cfg::M >> Cfg::logr(p);
+    if (xr_layout<Cfg, p>() == 1) return (i * Cfg::TF + j * sin) >> 4;
+    if (xr_layout<Cfg, p>() == 2) return i * Cfg::TF + j * sin;
+    return i * pstride<Cfg>(Cfg::TF) + j * pstride<Cfg>(sin);
+}
+// units of the frame area an exchange layout touches
+template <class Cfg> constexpr int x_layout_units(int layout) { return layout == 1 ? Cfg::X1_PITCH * 15 + Cfg::TF : (layout == 2 ? Cfg::M : Cfg::phys(Cfg::M - 1) + 1); }
+
 template <class Cfg, int p> LRA_HD void pass_read(typename Cfg::cplx* v, Lds fr, int tf) {
     using C = typename Cfg::cplx;
-    constexpr int lr = Cfg::logr(p), r = 1 << lr, nb = Cfg::R >> lr, sin = Cfg::M >> lr, Q = 1 << Cfg::PADSHIFT;
-    if constexpr (affine_tf<Cfg>() && sin % Q == 0) {
-        const int base = Cfg::phys(tf) * (int)sizeof(C);
+    constexpr int lr = Cfg::logr(p), r = 1 << lr, nb = Cfg::R >> lr, sin = Cfg::M >> lr;
+    static_assert(xr_layout<Cfg, p>() == 0 || xr_affine<Cfg, p>(), "the exchange layouts have the affine form only");
+    static_assert(x_layout_units<Cfg>(xr_layout<Cfg, p>()) * (int)sizeof(C) <= Cfg::FRAME_BYTES, "exchange layout within the frame area");
+    if constexpr (xr_affine<Cfg, p>()) {
+        const int base = xr_base<Cfg, p>(tf) * (int)sizeof(C);
         LRA_UNROLL
         for (int i = 0; i < nb; ++i) {
             LRA_UNROLL
-            for (int j = 0; j < r; ++j) v[i * r + j] = lds_ld<C>(fr, base + (i * pstride<Cfg>(Cfg::TF) + j * pstride<Cfg>(sin)) * (int)sizeof(C));
+            for (int j = 0; j < r; ++j) v[i * r + j] = lds_ld<C>(fr, base + xr_off<Cfg, p>(i, j) * (int)sizeof(C));
         }
     } else {
         LRA_UNROLL
@@ -261,28 +318,13 @@ template <class Cfg, int p> LRA_HD void load_pass_twiddles(typename Cfg::cplx* t
 template <class Cfg, int p> LRA_HD void pass_write(const typename Cfg::cplx* v, Lds fr, int tf) {
     using C = typename Cfg::cplx;
     constexpr int lr = Cfg::logr(p), r = 1 << lr, nb = Cfg::R >> lr, s = 1 << Cfg::logs(p);
-    constexpr bool last = p == Cfg::P - 1;  // then b < s, so k = b and the output position is b + j s
-    if constexpr (affine_tf<Cfg>() && p == 0) {
-        // s = 1, k = 0: position b r + j with b r a multiple of Q = r: phys = b (r + 1) + j
-        const int base = tf * (r + 1) * (int)sizeof(C);
+    static_assert(xw_layout<Cfg, p>() == 0 || xw_affine<Cfg, p>(), "the exchange layouts have the affine form only");
+    if constexpr (xw_affine<Cfg, p>()) {
+        const int base = xw_base<Cfg, p>(tf) * (int)sizeof(C);
         LRA_UNROLL
         for (int i = 0; i < nb; ++i) {
             LRA_UNROLL
-            for (int j = 0; j < r; ++j) lds_st<C>(fr, base + (i * Cfg::TF * (r + 1) + j) * (int)sizeof(C), v[i * r + j]);
-        }
-    } else if constexpr (affine_tf<Cfg>() && p > 0 && (last || Cfg::TF % s == 0)) {
-        int base;
-        if (last) {
-            base = Cfg::phys(tf) * (int)sizeof(C);  // position tf + i TF + j s
-        } else {
-            const int k = tf & (s - 1);  // TF % s == 0: k does not depend on i
-            base = Cfg::phys(((tf - k) << lr) + k) * (int)sizeof(C);
-        }
-        constexpr int istep = last ? pstride<Cfg>(Cfg::TF) : pstride<Cfg>(Cfg::TF << lr);
-        LRA_UNROLL
-        for (int i = 0; i < nb; ++i) {
-            LRA_UNROLL
-            for (int j = 0; j < r; ++j) lds_st<C>(fr, base + (i * istep + j * pstride<Cfg>(s)) * (int)sizeof(C), v[i * r + j]);
+            for (int j = 0; j < r; ++j) lds_st<C>(fr, base + xw_off<Cfg, p>(i, j) * (int)sizeof(C), v[i * r + j]);
         }
     } else {
         LRA_UNROLL

@@ -301,13 +301,14 @@ template <class Cfg, int HD> LRA_HD void v2_pass0(bool live, int tf, Regs2<Cfg, 
 // phase: inputs of the last pass for butterflies tf (v[0 .. rl)) and its mirror (v[rl .. 2 rl))
 template <class Cfg, int HD> LRA_HD void v2_last_read(Regs2<Cfg, HD>& rg, Lds fr, int tf) {
     using C = typename Cfg::cplx;
-    constexpr int p = Cfg::P - 1, lr = Cfg::logr(p), r = 1 << lr, sin = Cfg::M >> lr;
-    const int bA = Cfg::phys(tf) * (int)sizeof(C);
-    const int bB = Cfg::phys(v2_mirror_bfly<Cfg>(tf)) * (int)sizeof(C);
+    constexpr int p = Cfg::P - 1, lr = Cfg::logr(p), r = 1 << lr;
+    static_assert(xr_affine<Cfg, p>(), "v2_cfg_ok: base + immediates (lra_fft.h, exchange addresses)");
+    const int bA = xr_base<Cfg, p>(tf) * (int)sizeof(C);
+    const int bB = xr_base<Cfg, p>(v2_mirror_bfly<Cfg>(tf)) * (int)sizeof(C);
     LRA_UNROLL
     for (int j = 0; j < r; ++j) {
-        rg.v[j] = lds_ld<C>(fr, bA + j * pstride<Cfg>(sin) * (int)sizeof(C));
-        rg.v[r + j] = lds_ld<C>(fr, bB + j * pstride<Cfg>(sin) * (int)sizeof(C));
+        rg.v[j] = lds_ld<C>(fr, bA + xr_off<Cfg, p>(0, j) * (int)sizeof(C));
+        rg.v[r + j] = lds_ld<C>(fr, bB + xr_off<Cfg, p>(0, j) * (int)sizeof(C));
     }
 }
 

@@ -252,6 +252,9 @@ template <class Cfg> LRA_HD void pc_consumer_prologue(const StftArgs<typename Cf
         }
     }
     rg.pw_extra = (T)0;
+    // the constant zero pair that absent pieces address: nothing else writes the slot (the running sums have the area to themselves here), so once
+    // per workgroup, ahead of the frame loop's first fence, instead of one masked store per served frame
+    if (tf == 0) lds_st<C>(lds_sub(wg, PcLayout<Cfg>::rs_off()), a.melr_zero, mk<T>((T)0, (T)0));
 }
 // a producer's power row -> this thread's two runs (as v2_mel_runs_read)
 template <class Cfg> LRA_HD void pc_runs_read(PcRegs<Cfg>& rg, Lds pwr) {
@@ -282,10 +285,7 @@ template <class Cfg> LRA_HD void pc_accumulate(const StftArgs<typename Cfg::real
             lds_st<C>(rs, (jj * mel_runs_pitch(TF, 1) + tf) * (int)sizeof(C), acc);
         }
     }
-    if (tf == 0) {
-        lds_st<C>(rs, a.melr_mid, mk<T>(rg.wq.x * rg.pw_extra, rg.wq.y * rg.pw_extra));
-        lds_st<C>(rs, a.melr_zero, mk<T>((T)0, (T)0));
-    }
+    if (tf == 0) lds_st<C>(rs, a.melr_mid, mk<T>(rg.wq.x * rg.pw_extra, rg.wq.y * rg.pw_extra));  // (the zero slot: written once, pc_consumer_prologue)
 }
 // mel[m] of bands 2 tf, 2 tf + 1 for producer S's frame (as melr_combine with the register tile; `wg`: the workgroup's LDS, which rg.mad addresses)
 // UNI: pc_tile_uniform holds (the tile slot is rg.ph[S][b] + it, one value per wave)
