@@ -2,9 +2,11 @@
 
 The library holds several hundred instances of the fused kernels; hipcc compiles one translation unit on
 one core, so the instances are split into groups (``csrc/lra_fused.h``) that are compiled side by side:
-``lra_inst.hip`` once per group plus the units of ``UNITS`` below -- ``lra_api.hip`` (host API, general rocFFT path) and one
-``lra_<feature>_inst.hip`` per family of kernels with a translation unit of its own (mixed-radix transforms, tempogram, beat
-tracker, peak picker, chroma, pitch tracker and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA, neighbour graphs) -- then one link.  The
+``lra_inst.hip`` once per group plus the units of ``UNITS`` below -- ``lra_api.hip`` (host API of the transforms and everything without a unit
+of its own, general rocFFT path; it declares the fused kernels and compiles none of them) and one ``lra_<feature>_inst.hip`` per family of
+kernels, with the family's launchers and C entry points (mixed-radix transforms, tempogram, beat tracker, peak picker, chroma, pitch tracker
+and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA, neighbour graphs) -- then one link with ``-z defs``: a fused instance
+that the API unit launches and ``lra_fused.h`` does not list is an undefined symbol there, not at ``dlopen``.  The
 result ``librosa_amd/_liblibrosa_amd.so`` is git-ignored but travels to the GPU box with the repo snapshot.
 hipcc cross-compiles for gfx950 without a GPU.
 """
@@ -71,7 +73,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT):
         compiling = "-c" in cmd
         if compiling:
             # one object per translation unit, rebuilt only when one of the files it actually includes changed (depfile) -- a change
-            # to lra_api.hip or to a header only it includes costs one compile, not the eleven instance groups
+            # to lra_api.hip or to a header only it includes costs one compile, not the instance groups
             if not force and _deps_fresh(obj, line):
                 return obj
             cmd = [*cmd, "-MD", "-MF", obj + ".d"]
@@ -90,7 +92,7 @@ def build(force=False, verbose=True, extra_flags=(), out=OUT):
         objs = list(pool.map(run, jobs))
     # (freshness is judged per object from its depfile: a library linked while a source was being edited is older than that edit's object)
     if force or not os.path.exists(out) or any(os.path.getmtime(o) > os.path.getmtime(out) for o in objs):
-        link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs, f"-L{ROCM}/lib", "-lrocfft", f"-Wl,-rpath,{ROCM}/lib"]
+        link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *objs, f"-L{ROCM}/lib", "-lrocfft", f"-Wl,-rpath,{ROCM}/lib", "-Wl,-z,defs"]
         run(link)
     return out
 

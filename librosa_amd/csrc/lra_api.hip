@@ -7,6 +7,11 @@
 //   * any other n_fft (the reference's tests use 501, 755, 1023, 1025, 2049): a framing kernel +
 //     rocFFT batched R2C/C2R + small elementwise kernels.
 // No CPU fallback exists: without a device every entry point that touches data fails.
+//
+// Not in this file: the entry points of the feature families that have a translation unit of their own (tempogram, beat, peaks, chroma, pitch,
+// viterbi, dtw, rqa, knn, yin, pyin) are defined beside their kernels in lra_<feature>_inst.hip; lra_internal.h holds what those units share
+// with this one (the context, the error macros, device binding).  The fused power-of-two kernels are declared here and compiled in lra_inst.hip.
+// Comments of the form [sel:name] / [geo:name] are anchors that tests/geometry_cases.py cites in place of line numbers.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
@@ -23,6 +28,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/librosa_amd.h"
@@ -37,120 +43,23 @@
 #include "lra_probe.h"
 #include "lra_rng.h"
 #include "lra_mixed_launch.h"
-#include "lra_rhythm_launch.h"
-#include "lra_beat_launch.h"
-#include "lra_peaks_launch.h"
-#include "lra_chroma_launch.h"
-#include "lra_pitch_launch.h"
-#include "lra_pyin_launch.h"
-#include "lra_viterbi_launch.h"
-#include "lra_dtw_launch.h"
-#include "lra_rqa_launch.h"
-#include "lra_knn_launch.h"
-#include "lra_yin_launch.h"
+#include "lra_internal.h"
 
 using namespace lra;
 
 // ------------------------------------------------------------------------------------------------
-// error plumbing
+// error plumbing (the macros: lra_internal.h)
 // ------------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
+static thread_local std::string g_err;  // the one error slot: every unit's failures arrive here through lra::fail
 
-static int fail(int code, const std::string& msg) {
+int lra::fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-#define LRA_HIP(expr)                                                                                        \
-    do {                                                                                                     \
-        hipError_t e__ = (expr);                                                                             \
-        if (e__ != hipSuccess) return fail(LRA_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
-#define LRA_FFT(expr)                                                                                        \
-    do {                                                                                                     \
-        rocfft_status s__ = (expr);                                                                          \
-        if (s__ != rocfft_status_success) return fail(LRA_EROCFFT, std::string(#expr) + ": rocfft status " + std::to_string((int)s__)); \
-    } while (0)
-#define LRA_TRY(expr)              \
-    do {                           \
-        int rc__ = (expr);         \
-        if (rc__ != LRA_OK) return rc__; \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
-// objects
+// objects (lra_ctx: lra_internal.h)
 // ------------------------------------------------------------------------------------------------
-struct lra_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    int n_cu = 256;
-    int opt_stft_iters = 0;          // 0 = auto
-    int opt_istft_strip_groups = 0;  // 0 = auto
-    int opt_variant = -1;            // kernel tuning variant (f32 n_fft = 2048 only); -1 = per-mode default
-    int opt_autotune = 1;            // variant -1: time the candidate variants on the first large call of a plan and keep the faster
-    int opt_mel_runs = 1;            // use the run-ordered two-slope epilogue (OUT_MELR) where it applies
-    int opt_mel_tile = 0;            // frames staged per mel row before a flush (0 = auto)
-    int opt_generic_mel = 0;         // force the generic banded mel path (tests)
-    int opt_lds_pad = 0;             // extra dynamic LDS per workgroup (occupancy experiments)
-    int opt_v2 = 1;                  // second-generation forward kernel where it applies (lra_kernels2.h)
-    int opt_istft16 = 0;             // inverse, n_fft = 2048 f32, hop = n_fft / {2, 4, 8, 16}: radices 4, 16, 16 with 16-byte spectrum loads (variant 7) instead of 8, 8, 16
-    int opt_placement_retry = 0;     // lra_malloc_placed: candidate allocations to time before keeping the best (0 = its `tries` argument decides)
-    struct PlacedAlloc {             // one lra_malloc_placed result: a reserved virtual range backed by physical handles created and mapped in order
-        size_t padded = 0;
-        std::vector<hipMemGenericAllocationHandle_t> handles;
-        bool plain = false;          // an ordinary hipMalloc block (candidates of both kinds compete: which kind lands better differs from box to box)
-    };
-    std::map<void*, PlacedAlloc> placed;
-    std::mutex placed_mu;            // lra_free_placed may arrive from a finaliser thread while another call allocates
-    // ROCm 7.0 / gfx950, measured (scripts/vmm_coherence.hip, profiles/r06_experiments.md 3): hipMemAddressFree of one reserved range -- or mapping new physical
-    // memory into a range that was mapped before -- leaves OTHER live ranges with stale translations (kernels and hipMemcpy read old data: silent corruption).
-    // Ranges that are reserved once, never re-used and never freed while anything of this context is alive are clean under any amount of churn.  So: every
-    // candidate gets a fresh reservation, a released buffer keeps its (now empty) range until lra_ctx_destroy, and the address space spent that way is budgeted.
-    std::vector<std::pair<void*, size_t>> placed_retired;   // reserved ranges whose physical memory is gone: freed at lra_ctx_destroy
-    size_t placed_va_spent = 0;
-    static constexpr size_t kPlacedVaBudget = (size_t)4 << 40;  // 4 TiB of address space per context, then lra_malloc_placed declines (callers fall back to an ordinary allocation)
-    double placed_best_gbps = 0.0;   // best write-stream rate any candidate of this context has shown (the early-exit yardstick)
-    int opt_v3 = 1;                  // n_fft = 2048 f32: the radix 16-16-4 form with 16-byte row pieces (variant 6, lra_kernels2.h third form); 1: complex epilogue, 2: |X|^p too
-                                     // (measured on two boxes, same buffer, alternating (profiles/r06_raw/c_*, d_*): complex STFT -1.3 % ... -2.0 %, |X|^2 +1 %, hence complex only)
-    int opt_mel_pc = 1;              // fused mel, n_fft = 2048 f32: the producer / consumer kernel (lra_kernels_pc.h) instead of stft2_kernel<OUT_MELR>
-                                     // (-0.8 ... -1.9 % against the one-wave kernel on four boxes (profiles/r06_raw), never slower)
-    int opt_mel_many = 1;            // mel plans of n_fft = 512 with more than 64 bands are built for the eight-bands-per-thread kernel shape (read at lra_mel_plan_create)
-    int opt_cqt_merge = 1;           // lra_cqt_recursion_exec: 1 = octaves 1-2 in one launch beside the later halvings, 3 .. in one launch behind the chain (round 6); 2 = octaves 1 .. in one launch per frame length behind the chain (round 5); 0 = one launch per octave on the side stream
-    int opt_hpss_tile = 1;           // hpss: a thread per 4 x 4 tile with shared sorted cores (hpss_tile_kernel); 0: a thread per element (A/B)
-    int opt_mixed_inv_pow2 = 1;      // inverse, n_fft = 256 / 512 / 1024 with a hop outside n_fft / {2, 4, 8, 16}: the fused gather kernel of lra_mixed.h (0: istft_kernel's general mode)
-    int opt_mixed_pow2_mel = 1;      // fused mel at n_fft 128 / 256: the flat-index kernel of lra_mixed.h instead of the register-tiled one (0: A/B)
-    int opt_ola4 = 1;                // general inverse path: four output samples per thread in the gather kernel (0: one, A/B)
-    int opt_mixed_irfft = 1;         // listed mixed-radix lengths too long for the fused gather kernel: mixed_irfft_kernel + ola_gather_kernel instead of spec_pack + rocFFT + ola_gather (0: A/B)
-    int opt_mixed = 1;               // fused mixed-radix forward kernel for the listed non-power-of-two frame lengths (lra_mixed.h); 0: rocFFT path; 2: fused, mel band table read through the caches instead of staged in LDS (A/B)
-    int opt_direct = 1;              // direct framing (no ring) for hop >= n_fft
-    int opt_xcd_remap = 1;           // workgroup -> work item map that keeps neighbouring strips on one XCD (lra_kernels.h, xcd_block)
-    unsigned int* d_flag = nullptr;  // non-finite input flag (device)
-    std::map<std::pair<int, int>, std::pair<void*, void*>> cqt_tw;  // (n_fft, dtype) -> (W_M^t, W_N^k) of the fused constant-Q octave kernel (lra_mixed.h)
-    std::string name;
-    struct HostPipe* pipe = nullptr;  // staging of the host-buffer entry points (lra_stft_exec_host), created on first use
-    hipStream_t side_stream = nullptr;  // lra_ctx_side: a second stream for work that may overlap the main chain (created on first fork)
-    hipStream_t side_main = nullptr;    // the stream to return to
-    // fork: an event recorded on the main stream, waited for by the side stream; join: recorded on the side stream, waited for by the main one.
-    // Every fork takes the NEXT event of a ring (a constant-Q call forks once per octave): an event is never re-recorded while the side stream may
-    // still hold an unconsumed wait on its previous record -- `side_passed[i]`, recorded on the side stream right behind that wait, is synchronised
-    // before slot i is used again (it has normally completed long before).  ADVICE r04: one re-recorded event let such a wait slip on ROCm 7.0.
-    static constexpr int kForkRing = 16;
-    hipEvent_t fork_event[kForkRing] = {}, side_passed[kForkRing] = {};
-    bool fork_used[kForkRing] = {};
-    int fork_next = 0;
-    // join: the same treatment in the other direction -- back-to-back transforms no longer synchronise with the host between calls, so call
-    // k + 1's join could re-record a single join event while the main stream's wait on call k's record is still queued.  A ring of join events;
-    // `main_passed[i]`, recorded on the main stream right behind its wait, is synchronised before slot i is recorded again.
-    static constexpr int kJoinRing = 8;
-    hipEvent_t join_event[kJoinRing] = {}, main_passed[kJoinRing] = {};
-    bool join_used[kJoinRing] = {};
-    int join_next = 0;
-    bool on_side = false, side_used = false;
-    struct ResampleFft* rs_fft = nullptr;  // whole-signal transforms of lra_resample_fft_exec, created on first use
-    int opt_pipe_chunk_mb = 128;      // bytes (in + out) one pipeline stage moves
-    int opt_pipe_threads = 8;         // host threads per staging copy
-};
-
 // Two-slot staging between pageable host buffers and the device for the host-buffer entry points: pinned buffers the DMA
 // engines read / write at link rate, device buffers that persist across calls (a streaming caller -- stft(center=False,
 // out=D) per block -- allocates nothing after its first block), one stream per direction next to the compute stream.
@@ -223,61 +132,10 @@ struct FftPlanCache {
     }
 };
 
-struct Scratch {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t need) {
-        if (need <= bytes) return LRA_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        LRA_HIP(hipMalloc(&p, need));
-        bytes = need;
-        return LRA_OK;
-    }
-    ~Scratch() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 std::once_flag g_rocfft_once;
 void rocfft_setup_once() {
     std::call_once(g_rocfft_once, [] { rocfft_setup(); });
 }
-
-int upload(void** dptr, const void* host, size_t bytes) {
-    *dptr = nullptr;
-    LRA_HIP(hipMalloc(dptr, bytes ? bytes : 16));
-    if (bytes) LRA_HIP(hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice));
-    return LRA_OK;
-}
-
-// Every entry point runs with the context's device current and puts the caller's device back on exit: a torch
-// process that calls in with cuda:0 current and a tensor on cuda:1 (or a NumPy call that defaults to LOCAL_RANK's
-// device) must not find its own current device changed behind its back.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) {
-            err = hipSetDevice(device);
-            switched = err == hipSuccess;
-        }
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define LRA_BIND(ctxptr)                                                                                       \
-    if (!(ctxptr)) return fail(LRA_EINVAL, "null context");                                                    \
-    DeviceGuard device_guard__((ctxptr)->device);                                                              \
-    if (device_guard__.err != hipSuccess) return fail(LRA_EHIP, std::string("selecting the context's device: ") + hipGetErrorString(device_guard__.err))
-
-inline size_t real_bytes(int dtype) { return dtype == LRA_F64 ? 8 : 4; }
 
 }  // namespace
 
@@ -382,55 +240,58 @@ template <class T> struct StftLaunch {
     hipStream_t stream = nullptr;
     hipError_t err = hipSuccess;
 
+    // The instance of a kernel family for the call's power mode; `inst(pm)` names the instance of compile-time power mode decltype(pm)::value.  The complex
+    // epilogue raises nothing to a power and exists as POW_TWO only, so nothing else is named for it (a named instance has to be in lra_fused.h's lists).
+    using Kern = void (*)(StftArgs<T>, const T*, void*);
+    template <int MODE, class F> Kern pick_power(F inst) const {
+        if constexpr (MODE != OUT_COMPLEX) {
+            if (a.power_mode == POW_ONE) return inst(std::integral_constant<int, POW_ONE>{});
+            if (a.power_mode == POW_GENERAL) return inst(std::integral_constant<int, POW_GENERAL>{});
+        }
+        return inst(std::integral_constant<int, POW_TWO>{});
+    }
+    template <class Cfg, int MODE, int RA> Kern ring_kernel() const {
+        return pick_power<MODE>([](auto pm) -> Kern { return stft_kernel<Cfg, MODE, decltype(pm)::value, RA>; });
+    }
+    template <class Cfg, int HD, int MODE> Kern v2_kernel() const {
+        return pick_power<MODE>([](auto pm) -> Kern { return stft2_kernel<Cfg, HD, MODE, decltype(pm)::value>; });
+    }
+
     template <class Cfg, int MODE> void launch(int shared_bytes) {
         static_assert(Cfg::P <= 4, "at most four Stockham passes are wired up");
         const int lds_probe_v1 = Cfg::FPB * stft_slot_bytes<Cfg>(MODE, a.n_mels, mel_tile_opt > 0 ? mel_tile_opt : 4) + shared_bytes + lds_pad;
-        void (*kern)(StftArgs<T>, const T*, void*) = nullptr;
+        Kern kern = nullptr;
         bool direct = false;
         if constexpr (Cfg::PLAN == 0) {  // (the radix 16-16-4 configuration has second-generation instances only)
-        kern = stft_kernel<Cfg, MODE, POW_TWO, 0>;
-        if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, 0>;
-        if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, 0>;
-        if constexpr (sizeof(T) == 4) {  // row-aligned hops (n_fft/4, n_fft/8, ...): the fast ring addressing, f32 only
-            if (ring_rows_aligned<Cfg>(a.hop)) {
-                kern = stft_kernel<Cfg, MODE, POW_TWO, 1>;
-                if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, 1>;
-                if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, 1>;
-            }
+        kern = ring_kernel<Cfg, MODE, 0>();  // [sel:ring]
+        if constexpr (sizeof(T) == 4) {  // row-aligned hops (n_fft/4, n_fft/8, ...): the fast ring addressing, f32 only  // [sel:ringrows-f32]
+            if (ring_rows_aligned<Cfg>(a.hop)) kern = ring_kernel<Cfg, MODE, 1>();  // [sel:ringrows]
         }
         // hop >= n_fft (frames do not overlap): direct framing, no ring (complex / power epilogues)
         if constexpr (MODE == OUT_COMPLEX || MODE == OUT_POWER) {
-            if (a.hop >= Cfg::N && use_direct) {
+            if (a.hop >= Cfg::N && use_direct) {  // [sel:direct]
                 direct = true;
-                kern = stft_kernel<Cfg, MODE, POW_TWO, 2>;
-                if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, 2>;
-                if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, 2>;
+                kern = ring_kernel<Cfg, MODE, 2>();
             }
         }
         // n_fft >= 8192 (f32) with hop = n_fft / {2, 4, 8, 16}: the sample ring lives in registers (RA = 2 + log2 HD)
         if constexpr ((MODE == OUT_COMPLEX || MODE == OUT_POWER) && sizeof(T) == 4 && (Cfg::LOGM >= 12 || Cfg::LOGM == 7 || Cfg::LOGM == 8)) {
-            const int hd = use_direct ? regring_hd<Cfg>(a.hop) : 0;
-#define LRA_PICKR(RAM)                                                                                       \
-    kern = stft_kernel<Cfg, MODE, POW_TWO, RAM>;                                                            \
-    if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft_kernel<Cfg, MODE, POW_ONE, RAM>;        \
-    if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft_kernel<Cfg, MODE, POW_GENERAL, RAM>;
-            if (hd == 2) { direct = true; LRA_PICKR(3) } else if (hd == 4) { direct = true; LRA_PICKR(4) } else if (hd == 8) { direct = true; LRA_PICKR(5) } else if (hd == 16) { direct = true; LRA_PICKR(6) }
-#undef LRA_PICKR
+            const int hd = use_direct ? regring_hd<Cfg>(a.hop) : 0;  // [sel:regring]
+            if (hd) direct = true;
+            if (hd == 2) kern = ring_kernel<Cfg, MODE, 3>();
+            else if (hd == 4) kern = ring_kernel<Cfg, MODE, 4>();
+            else if (hd == 8) kern = ring_kernel<Cfg, MODE, 5>();
+            else if (hd == 16) kern = ring_kernel<Cfg, MODE, 6>();
         }
         }
         // Second-generation kernel (lra_kernels2.h) where it applies: complex / power epilogues, 16 points per thread with
-        // a two-butterfly last pass (n_fft 1024 / 2048 / 4096), hop = n_fft / {1, 2, 4, 8}.
+        // a two-butterfly last pass (n_fft 1024 / 2048 / 4096 / 16384), hop = n_fft / {1, 2, 4, 8}.
         bool v2 = false;
         if constexpr (v23_cfg_ok<Cfg>() && (MODE == OUT_COMPLEX || MODE == OUT_POWER || MODE == OUT_MELR)) {
             const int hd = (use_v2 && (MODE != OUT_MELR || mel_v2)) ? v2_hop_divisor<Cfg>(a.hop) : 0;
-            if (hd) {
+            if (hd) {  // [sel:v2]
                 v2 = true;
-#define LRA_PICK2(HD)                                                                                        \
-    kern = stft2_kernel<Cfg, HD, MODE, POW_TWO>;                                                            \
-    if (MODE != OUT_COMPLEX && a.power_mode == POW_ONE) kern = stft2_kernel<Cfg, HD, MODE, POW_ONE>;        \
-    if (MODE != OUT_COMPLEX && a.power_mode == POW_GENERAL) kern = stft2_kernel<Cfg, HD, MODE, POW_GENERAL>;
-                if (hd == 1) { LRA_PICK2(1) } else if (hd == 2) { LRA_PICK2(2) } else if (hd == 4) { LRA_PICK2(4) } else { LRA_PICK2(8) }
-#undef LRA_PICK2
+                kern = hd == 1 ? v2_kernel<Cfg, 1, MODE>() : hd == 2 ? v2_kernel<Cfg, 2, MODE>() : hd == 4 ? v2_kernel<Cfg, 4, MODE>() : v2_kernel<Cfg, 8, MODE>();
             }
         }
         if (!kern) { err = hipErrorInvalidValue; return; }
@@ -468,13 +329,13 @@ template <class T> struct StftLaunch {
         // several slots per wave (n_fft < 2048) with the row-aligned ring: keep the slots in step (frames per slot a
         // multiple of n_fft / hop = 4) so that the ring rotation is one scalar per wave
         a.rot_uniform = 0;
-        if (Cfg::FPB > 1 && Cfg::TF < 64 && ring_rows_aligned<Cfg>(a.hop)) {
+        if (Cfg::FPB > 1 && Cfg::TF < 64 && ring_rows_aligned<Cfg>(a.hop)) {  // [geo:rot-uniform]
             if (iters_opt <= 0 && iters >= 4) iters = (iters + 3) / 4 * 4;
             a.rot_uniform = iters % 4 == 0;
         }
         a.mel_tile = mel_tile_opt > 0 ? mel_tile_opt : 4;
-        if (a.mel_tile > iters) a.mel_tile = iters;
-        a.frames_per_wg = Cfg::FPB * iters;
+        if (a.mel_tile > iters) a.mel_tile = iters;  // [geo:mel-tile]
+        a.frames_per_wg = Cfg::FPB * iters;  // [geo:strips]
         a.wg_per_clip = (a.n_frames + a.frames_per_wg - 1) / a.frames_per_wg;
         a.slot_bytes = v2 ? stft2_slot_bytes<Cfg>() : direct ? Cfg::FRAME_BYTES : stft_slot_bytes<Cfg>(MODE, a.n_mels, a.mel_tile);
         a.shared_off = Cfg::FPB * a.slot_bytes;
@@ -487,7 +348,7 @@ template <class T> struct StftLaunch {
             if (err != hipSuccess) return;
         }
         a.n_blocks = (int)grid;
-        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;
+        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;  // [geo:xcd-pad]
         const long long launch_grid = a.xcd_chunk ? 8LL * a.xcd_chunk : grid;
         hipLaunchKernelGGL(kern, dim3((unsigned)launch_grid), dim3(Cfg::NT), lds, stream, a, a.y, out);
         err = hipGetLastError();
@@ -495,17 +356,12 @@ template <class T> struct StftLaunch {
 
     // Producer / consumer fused mel kernel (lra_kernels_pc.h): 192-thread workgroups [P, P, C], NP = 2 frame slots each.  Geometry as above:
     // strips of 24..176 frames per slot, the grid a whole number of rounds of resident workgroups (four per CU).
-    template <class Cfg> void launch_pc(int hd) {
+    template <class Cfg> void launch_pc(int hd) {  // [sel:launch-pc]
         using PL = PcLayout<Cfg>;
-        void (*kern)(StftArgs<T>, const T*, void*) = nullptr;
-#define LRA_PICKP(HD)                                                        \
-    kern = stft_pc_kernel<Cfg, HD, POW_TWO>;                                 \
-    if (a.power_mode == POW_ONE) kern = stft_pc_kernel<Cfg, HD, POW_ONE>;    \
-    if (a.power_mode == POW_GENERAL) kern = stft_pc_kernel<Cfg, HD, POW_GENERAL>;
-        if (hd == 4) { LRA_PICKP(4) } else { LRA_PICKP(8) }
-#undef LRA_PICKP
+        const Kern kern = hd == 4 ? pick_power<OUT_MEL2>([](auto pm) -> Kern { return stft_pc_kernel<Cfg, 4, decltype(pm)::value>; })
+                                  : pick_power<OUT_MEL2>([](auto pm) -> Kern { return stft_pc_kernel<Cfg, 8, decltype(pm)::value>; });
         const int lds = PL::BYTES + lds_pad;
-        constexpr int fpb = PL::NP;
+        constexpr int fpb = PL::NP;  // [geo:pc-np]
         int iters = iters_opt;
         if (iters <= 0) {
             const int per_cu = resident_workgroups(reinterpret_cast<const void*>(kern), PL::NT, lds);
@@ -525,14 +381,14 @@ template <class T> struct StftLaunch {
         if (iters < 1) iters = 1;
         a.rot_uniform = 0;
         a.mel_tile = 1;
-        a.frames_per_wg = fpb * iters;
+        a.frames_per_wg = fpb * iters;  // [geo:pc-strips]
         a.wg_per_clip = (a.n_frames + a.frames_per_wg - 1) / a.frames_per_wg;
         a.slot_bytes = PL::FRAME;
         a.shared_off = 0;
         const long long grid = batch * a.wg_per_clip;
         if (grid > 0x7ffffff0LL) { err = hipErrorInvalidConfiguration; return; }
         a.n_blocks = (int)grid;
-        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;
+        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;  // [geo:pc-xcd-pad]
         const long long launch_grid = a.xcd_chunk ? 8LL * a.xcd_chunk : grid;
         hipLaunchKernelGGL(kern, dim3((unsigned)launch_grid), dim3(PL::NT), lds, stream, a, a.y, out);
         err = hipGetLastError();
@@ -542,7 +398,7 @@ template <class T> struct StftLaunch {
         if constexpr (Cfg::REV) {  // the ascending-radix configurations exist for the inverse kernel only
             err = hipErrorInvalidValue;
             return;
-        } else if constexpr (Cfg::PLAN == 1) {  // radices 16, 16, 4: second-generation kernels only (stft_run selects the variant where they apply)
+        } else if constexpr (Cfg::PLAN == 1) {  // radices 16, 16, 4: second-generation kernels only (stft_run selects the variant where they apply)  // [sel:plan1]
             if (!use_v2 || v2_hop_divisor<Cfg>(a.hop) == 0) { err = hipErrorInvalidValue; return; }
             if (mode == OUT_COMPLEX) launch<Cfg, OUT_COMPLEX>(0);
             else if (mode == OUT_POWER) launch<Cfg, OUT_POWER>(0);
@@ -570,7 +426,7 @@ template <class T> struct StftLaunch {
             // n_fft = 2048, float32, banks of up to 128 bands with pair segments of at most four pieces: producer and consumer waves (lra_kernels_pc.h)
             if constexpr (pc_cfg_ok<Cfg>()) {
                 const int hd_pc = v2_hop_divisor<Cfg>(a.hop);
-                if (mel_pc && mel && mel->melr2_ok && mel_runs && use_v2 && pc_bank_ok<Cfg>(a.n_mels, mel->melr2_pmax) && pc_fits_budget<Cfg>(hd_pc, a.power_mode)) {
+                if (mel_pc && mel && mel->melr2_ok && mel_runs && use_v2 && pc_bank_ok<Cfg>(a.n_mels, mel->melr2_pmax) && pc_fits_budget<Cfg>(hd_pc, a.power_mode)) {  // [sel:mel-pc]
                     a.melr_w = (const T*)mel->d_melr2_w;
                     a.melr_keep = (const T*)mel->d_melr2_keep;
                     a.melr_addr = mel->d_melr2_addr;
@@ -583,7 +439,7 @@ template <class T> struct StftLaunch {
             }
             // first choice: the run-ordered form (no per-lane control flow, no (wA P, wB P) round trip through LDS)
             if constexpr (v2_cfg_ok<MC>()) {
-                if (mel && mel->melr2_ok && mel_runs && use_v2 && melr_fits<MC>() && v2_hop_divisor<MC>(a.hop) > 0) {
+                if (mel && mel->melr2_ok && mel_runs && use_v2 && melr_fits<MC>() && v2_hop_divisor<MC>(a.hop) > 0) {  // [sel:mel-onewave]
                     const int shared_r = melr_shared_bytes<MC>(a.n_mels, mel->melr2_pmax);
                     if (MC::FPB * stft2_slot_bytes<MC>() + shared_r <= 160 * 1024) {
                         a.melr_w = (const T*)mel->d_melr2_w;
@@ -601,7 +457,7 @@ template <class T> struct StftLaunch {
             }
             if constexpr (mel_many_applies<Cfg>()) {
                 using MM = typename MelManyCfgOf<Cfg>::type;
-                if (mel && mel->melr_ok && mel->melr_many && mel_runs && melr_fits<MM>()) {
+                if (mel && mel->melr_ok && mel->melr_many && mel_runs && melr_fits<MM>()) {  // [sel:mel-many]
                     const int shared_m = melr_shared_bytes<MM>(a.n_mels, mel->melr_pmax);
                     if (MM::FPB * stft_slot_bytes<MM>(OUT_MELR, a.n_mels, 1) + shared_m <= 160 * 1024) {
                         a.melr_w = (const T*)mel->d_melr_w;
@@ -616,7 +472,7 @@ template <class T> struct StftLaunch {
                     }
                 }
             }
-            if (mel && mel->melr_ok && !mel->melr_many && mel_runs && melr_fits<MC>() && MC::R == 16) {
+            if (mel && mel->melr_ok && !mel->melr_many && mel_runs && melr_fits<MC>() && MC::R == 16) {  // [sel:mel-runs]
                 const int shared_r = melr_shared_bytes<MC>(a.n_mels, mel->melr_pmax);
                 // no LDS staging tile by default: the kernel keeps the last 8 frames of each band in registers and stores them as one burst
                 int tile_r = mel_tile_opt > 0 ? mel_tile_opt : 1;
@@ -635,10 +491,10 @@ template <class T> struct StftLaunch {
             }
             const int shared = mel2_shared_bytes<MC>(a.n_mels);
             // largest staging tile (frames per flushed mel row) that still fits the 160 KiB of LDS
-            int tile = mel_tile_opt > 0 ? mel_tile_opt : 4;
+            int tile = mel_tile_opt > 0 ? mel_tile_opt : 4;  // [geo:staging-tile]
             while (tile > 1 && MC::FPB * stft_slot_bytes<MC>(OUT_MEL2, a.n_mels, tile) + shared > 160 * 1024) tile /= 2;
             const int pi = MC::R == 16 ? 1 : 0;
-            if (mel && mel2_fits<MC>(a.n_mels) && mel->n_pieces[pi] > 0 && mel->n_pieces[pi] <= MC::TF + a.n_mels + 2 &&
+            if (mel && mel2_fits<MC>(a.n_mels) && mel->n_pieces[pi] > 0 && mel->n_pieces[pi] <= MC::TF + a.n_mels + 2 &&  // [sel:mel-masked]
                 MC::FPB * stft_slot_bytes<MC>(OUT_MEL2, a.n_mels, tile) + shared <= 160 * 1024) {
                 a.mel_run = mel->d_run[pi];
                 a.mel_segd = mel->d_segd[pi];
@@ -647,7 +503,7 @@ template <class T> struct StftLaunch {
                 launch<MC, OUT_MEL2>(shared);
                 return;
             }
-            launch<Cfg, OUT_MEL>(0);  // generic banded path
+            launch<Cfg, OUT_MEL>(0);  // generic banded path  // [sel:mel-generic]
             return;
         }
         if (mode == OUT_COMPLEX) launch<Cfg, OUT_COMPLEX>(0);
@@ -669,7 +525,7 @@ template <class T> struct IstftLaunch {
         if constexpr (Cfg::PLAN == 1 && !Cfg::REV) {  // forward-only configuration (radices 16, 16, 4)
             err = hipErrorInvalidValue;
             return;
-        } else if constexpr (Cfg::PLAN == 1) {  // radices 4, 16, 16: the row-aligned overlap-add forms only (instances: HC = 8, 4, 2, 1)
+        } else if constexpr (Cfg::PLAN == 1) {  // radices 4, 16, 16: the row-aligned overlap-add forms only (instances: HC = 8, 4, 2, 1)  // [sel:istft-plan1]
             if (istft_rows_hc<Cfg>(a.hop) == 0) { err = hipErrorInvalidValue; return; }
             run<Cfg>();
         } else {
@@ -684,8 +540,8 @@ template <class T> struct IstftLaunch {
         a.drain_steps = N > H ? (N - H + H - 1) / H : 0;
         a.batch = batch;
         int lds = istft_lds_bytes<Cfg, 0>();
-        void (*kern)(IstftArgs<T>, const cx<T>*, const T*, T*) = istft_kernel<Cfg, 0>;
-        if constexpr (sizeof(T) == 4) {  // row-aligned overlap-add for hop = n_fft/2, n_fft/4 and n_fft/8 (f32)
+        void (*kern)(IstftArgs<T>, const cx<T>*, const T*, T*) = istft_kernel<Cfg, 0>;  // [sel:istft-general]
+        if constexpr (sizeof(T) == 4) {  // row-aligned overlap-add for hop = n_fft/2, n_fft/4 and n_fft/8 (f32)  // [sel:istft-rows]
             const int hc = istft_rows_hc<Cfg>(a.hop);
             if constexpr (Cfg::R >= 4) {
                 if (hc == Cfg::R / 2) { kern = istft_kernel<Cfg, Cfg::R / 2>; lds = istft_lds_bytes<Cfg, Cfg::R / 2>(); }
@@ -716,7 +572,7 @@ template <class T> struct IstftLaunch {
             }
             while (sf > 8 && (batch * ((a.n_used + sf - 1) / sf) + FPB - 1) / FPB < 2LL * n_cu) sf /= 2;  // small jobs: fill the chip first
         }
-        a.strip_frames = sf < 1 ? 1 : sf;
+        a.strip_frames = sf < 1 ? 1 : sf;  // [geo:istft-strips]
         a.strips_per_clip = (a.n_used + a.strip_frames - 1) / a.strip_frames;
         const long long grid = (batch * a.strips_per_clip + FPB - 1) / FPB;
         if (grid > 0x7ffffff0LL) { err = hipErrorInvalidConfiguration; return; }
@@ -725,7 +581,7 @@ template <class T> struct IstftLaunch {
             if (err != hipSuccess) return;
         }
         a.n_blocks = (int)grid;
-        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;
+        a.xcd_chunk = (xcd_remap && grid >= 64) ? (int)((grid + 7) / 8) : 0;  // [geo:istft-xcd-pad]
         const long long launch_grid = a.xcd_chunk ? 8LL * a.xcd_chunk : grid;
         hipLaunchKernelGGL(kern, dim3((unsigned)launch_grid), dim3(Cfg::NT), lds, stream, a, a.D, a.wss, a.y);
         err = hipGetLastError();
@@ -1169,7 +1025,7 @@ int stft_run(lra_stft_plan* p, int mode, const void* y, int64_t batch, int64_t n
             L.mel = mel;
         }
         L.a.nonfinite_flag = ctx->d_flag;
-        L.mode = (mode == OUT_MEL && mel && mel->two_slope && !ctx->opt_generic_mel) ? OUT_MEL2 : mode;
+        L.mode = (mode == OUT_MEL && mel && mel->two_slope && !ctx->opt_generic_mel) ? OUT_MEL2 : mode;  // [sel:generic-mel-option]
         L.batch = batch;
         L.stream = ctx->stream;
         L.iters_opt = ctx->opt_stft_iters;
@@ -1196,10 +1052,10 @@ int stft_run(lra_stft_plan* p, int mode, const void* y, int64_t batch, int64_t n
         // (the second-generation kernel replaces both tunings for the complex / power epilogues)
         bool v2_applies = false;
         if constexpr (sizeof(T) == 4)
-            v2_applies = ctx->opt_v2 && (L.mode == OUT_COMPLEX || L.mode == OUT_POWER) && p->logm == 10 && v2_hop_divisor<typename CfgSel<float, 10, 0>::type>(p->hop) > 0;
+            v2_applies = ctx->opt_v2 && (L.mode == OUT_COMPLEX || L.mode == OUT_POWER) && p->logm == 10 && v2_hop_divisor<typename CfgSel<float, 10, 0>::type>(p->hop) > 0;  // [sel:v2-applies]
         if (ctx->opt_variant < 0 && ctx->opt_autotune && sizeof(T) == 4 && p->logm == 10 && !v2_applies) {
             int& tuned = p->tuned_variant[L.mode & 3];
-            if (tuned < 0 && batch * n_frames >= 65536) LRA_TRY(autotune_variant(ctx, launch, &tuned));
+            if (tuned < 0 && batch * n_frames >= 65536) LRA_TRY(autotune_variant(ctx, launch, &tuned));  // [sel:autotune]
             if (tuned >= 0) variant = tuned;
         }
         bool pc_g = false;  // fused mel through the producer / consumer kernel on the radix 16-16-4 core (mel_pc = 2), where that kernel serves the bank and fits its register budget
@@ -1208,7 +1064,7 @@ int stft_run(lra_stft_plan* p, int mode, const void* y, int64_t batch, int64_t n
             if (L.mode == OUT_MEL2 && ctx->opt_mel_pc == 2 && p->logm == 10 && mel && mel->melr2_ok && ctx->opt_mel_runs && ctx->opt_v2 && (ctx->opt_variant < 0 || ctx->opt_variant == 6))
                 pc_g = pc_bank_ok<C6>(mel->n_mels, mel->melr2_pmax) && pc_fits_budget<C6>(v2_hop_divisor<C6>(p->hop), power_mode_of(power));
         }
-        if ((v2_applies && (ctx->opt_v3 == 2 || (ctx->opt_v3 == 1 && L.mode == OUT_COMPLEX)) && (ctx->opt_variant < 0 || ctx->opt_variant == 6)) || pc_g) variant = 6;
+        if ((v2_applies && (ctx->opt_v3 == 2 || (ctx->opt_v3 == 1 && L.mode == OUT_COMPLEX)) && (ctx->opt_variant < 0 || ctx->opt_variant == 6)) || pc_g) variant = 6;  // [sel:variant-fwd]
         else if (variant == 6) variant = 0;  // (the 16-16-4 form exists for the second-generation complex / power kernels and the producer / consumer mel kernel only)
         return launch(variant);
     }
@@ -1360,7 +1216,7 @@ int istft_run(lra_istft_plan* p, const void* D, int64_t batch, int64_t d_batch_s
         }
         return LRA_OK;
     };
-    if (p->pow2 && ctx->opt_mixed_inv_pow2 && p->d_mtw && p->hop * 2 != N && p->hop * 4 != N && p->hop * 8 != N && p->hop * 16 != N && p->hop < N) {
+    if (p->pow2 && ctx->opt_mixed_inv_pow2 && p->d_mtw && p->hop * 2 != N && p->hop * 4 != N && p->hop * 8 != N && p->hop * 16 != N && p->hop < N) {  // [sel:istft-mixed-pow2]
         bool done = false;
         LRA_TRY(run_mixed(&done));
         if (done) return LRA_OK;
@@ -1399,7 +1255,7 @@ int istft_run(lra_istft_plan* p, const void* D, int64_t batch, int64_t d_batch_s
         bool fused_first_pass = false;
         if constexpr (sizeof(T) == 4)
             fused_first_pass = ctx->opt_v2 && ctx->opt_variant < 0 && p->logm == 10 && istft_rows_hc<typename CfgSel<float, 10, 5>::type>(p->hop) > 0;
-        if (fused_first_pass) variant = ctx->opt_istft16 ? 7 : 5;  // 7: the same with 16-byte spectrum loads (radices 4, 16, 16)
+        if (fused_first_pass) variant = ctx->opt_istft16 ? 7 : 5;  // 7: the same with 16-byte spectrum loads (radices 4, 16, 16)  // [sel:variant-inv]
         bool too_big = false;
         auto launch = [&](int v) -> int {
             IstftLaunch<T> Lv = L;
@@ -2291,6 +2147,22 @@ int mixed_tables(int n_fft, int dtype, void** d_mtw, void** d_mtwn) {
 }
 }  // namespace
 
+extern "C++" {  // (lra_internal.h: shared with the feature units)
+int lra::ctx_twiddles(lra_ctx* ctx, int n_fft, int dtype, const void** tw_m, const void** tw_n) {
+    auto& tw = ctx->cqt_tw[std::make_pair(n_fft, dtype)];
+    if (!tw.first) LRA_TRY(mixed_tables(n_fft, dtype, &tw.first, &tw.second));
+    *tw_m = tw.first;
+    *tw_n = tw.second;
+    return LRA_OK;
+}
+
+int lra::read_status(lra_ctx* ctx, const void* dev, void* host, size_t bytes) {
+    LRA_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    LRA_HIP(hipStreamSynchronize(ctx->stream));
+    return LRA_OK;
+}
+}  // extern "C++"
+
 int lra_stft_plan_create(lra_ctx* ctx, int n_fft, int hop_length, const void* window_host, int center, int pad_mode, int dtype, lra_stft_plan** out) {
     LRA_BIND(ctx);
     if (!out) return fail(LRA_EINVAL, "null out");
@@ -2487,7 +2359,7 @@ int lra_mel_plan_create(lra_ctx* ctx, int n_mels, int n_bins, const void* basis_
                 if (rc == LRA_OK && (n_bins - 1) % 16 == 0) {
                     // n_fft = 512 with MANY bands: eight bands per thread (MelManyCfgOf).  Same box: 128 bands 1.54 -> 1.04 ms, but 80 bands 0.75 -> 1.18 (their wider pair segments need
                     // the longer hoisted lists of the four-band form; 97 bands 0.90 -> 1.02, 112 bands 1.23 -> 1.03): taken above 100 bands
-                    p->melr_many = ctx->opt_mel_many && (n_bins - 1) / 16 == 16 && n_mels > 100;
+                    p->melr_many = ctx->opt_mel_many && (n_bins - 1) / 16 == 16 && n_mels > 100;  // [sel:mel-many-plan]
                     MelRuns<float> mr = build_mel_runs<float>(ts, (n_bins - 1) / 16, 8, MELR_PMAX, melr_ph_of_tf((n_bins - 1) / 16, p->melr_many));  // (min list length = the hoisted prefix)
                     if (mr.ok) {
                         rc = upload(&p->d_melr_w, mr.w.data(), mr.w.size() * sizeof(float));
@@ -2987,930 +2859,6 @@ int lra_onset_exec(lra_ctx* ctx, const void* S, const void* ref, void* out, int6
                                                     amin, top_db, item_max, detrend, env);
 }
 
-// ---- tempogram / tempo (lra_rhythm.h, launched from lra_rhythm_inst.hip) ------------------------------------------------------------
-static_assert(rhythm::kWrite == LRA_TEMPOGRAM_WRITE && rhythm::kSum == LRA_TEMPOGRAM_SUM && rhythm::kArgmax == LRA_TEMPOGRAM_ARGMAX && rhythm::kNormNone == LRA_TEMPOGRAM_NORM_NONE &&
-                  rhythm::kNormInf == LRA_TEMPOGRAM_NORM_INF && rhythm::kNormL1 == LRA_TEMPOGRAM_NORM_L1 && rhythm::kNormL2 == LRA_TEMPOGRAM_NORM_L2,
-              "tempogram codes");
-static_assert(rhythm::transform_length(344) == 720 && rhythm::transform_length(384) == 800 && rhythm::transform_length(689) == 1440 && rhythm::transform_length(800) == 1600 &&
-                  rhythm::transform_length(2400) == 4800 && rhythm::transform_length(2401) == 0,
-              "tempogram transform lengths");
-
-int64_t lra_tempogram_work_bytes(int64_t batch, int64_t n_frames, int win_length, int mode) {
-    const int64_t groups = n_frames > 0 ? (n_frames + rhythm::kRhythmGroup - 1) / rhythm::kRhythmGroup : 0;
-    return 16 + (mode == LRA_TEMPOGRAM_SUM && batch > 0 && win_length > 0 ? batch * groups * (int64_t)win_length * 8 : 0);
-}
-
-int lra_tempogram_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, int win_length, int center, const void* window, int norm, int mode,
-                       const void* logprior, const void* bpms, void* out, void* work, int* nonfinite) {
-    LRA_BIND(ctx);
-    if (nonfinite) *nonfinite = 0;
-    if (mode < LRA_TEMPOGRAM_WRITE || mode > LRA_TEMPOGRAM_ARGMAX) return fail(LRA_EINVAL, "tempogram: unknown mode");
-    if (norm < LRA_TEMPOGRAM_NORM_NONE || norm > LRA_TEMPOGRAM_NORM_L2) return fail(LRA_EINVAL, "tempogram: unknown norm code");
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "tempogram: dtype must be LRA_F32 or LRA_F64");
-    if (win_length < 1) return fail(LRA_EINVAL, "tempogram: win_length must be a positive integer");
-    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "tempogram: negative size");
-    rhythm::Args a{};
-    const int geometry = rhythm::prepare(a, n, win_length, center, norm, mode);
-    if (geometry == mixed::kGeometryTooShort)
-        return fail(LRA_EINVAL, "tempogram: input is too short (n=" + std::to_string(n + 2 * (int64_t)a.pad) + ") for frame_length=" + std::to_string(win_length));
-    const int64_t n_frames = a.n_frames;
-    if (batch == 0 || n_frames == 0) return LRA_OK;
-    if (!env || !window || !out || !work) return fail(LRA_EINVAL, "null data pointer");
-    if (mode != LRA_TEMPOGRAM_WRITE && (!logprior || !bpms)) return fail(LRA_EINVAL, "tempogram: tempo modes need the prior and the BPM table");
-    if (n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames per clip");
-    if (geometry == mixed::kGeometryLds) return fail(LRA_EINVAL, "tempogram: win_length=" + std::to_string(win_length) + " does not fit the LDS of a workgroup");
-    a.env = env;
-    a.env_f64 = dtype == LRA_F64;
-    a.win = (const double*)window;
-    if (a.N > 0) {
-        auto& tw = ctx->cqt_tw[std::make_pair(a.N, (int)LRA_F64)];
-        if (!tw.first) LRA_TRY(mixed_tables(a.N, LRA_F64, &tw.first, &tw.second));
-        a.tw_m = (const mixed::cpx<double>*)tw.first;
-        a.tw_n = (const mixed::cpx<double>*)tw.second;
-    }
-    a.logprior = (const double*)logprior;
-    a.bpms = (const double*)bpms;
-    a.out = (double*)out;
-    a.flag = (int*)work;
-    a.partial = (double*)((char*)work + 16);
-    if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "tempogram: too many frames for one launch");
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(rhythm::launch_tempogram(a, batch, ctx->stream));
-    if (mode == LRA_TEMPOGRAM_SUM) {
-        rhythm::FinishArgs f{a.partial, a.logprior, a.bpms, a.out, n_frames, a.groups, win_length};
-        LRA_HIP(rhythm::launch_tempo_finish(f, batch, ctx->stream));
-    }
-    if (nonfinite) {
-        int h = 0;
-        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *nonfinite = h != 0;
-    }
-    return LRA_OK;
-}
-
-// ---- beat tracker (lra_beat.h, launched from lra_beat_inst.hip) ------------------------------------------------------------------------
-static_assert(beat::kPerRow == LRA_BEAT_BPM_PER_ROW && beat::kPerFrame == LRA_BEAT_BPM_PER_FRAME, "beat codes");
-
-namespace {
-struct BeatWork {
-    int64_t any, dead, fpb, norm, local, cum, backlink, order, total;
-};
-BeatWork beat_work_layout(int64_t batch, int64_t n, int bpm_mode) {
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t rows = batch > 0 ? batch : 0, cells = rows * (n > 0 ? n : 0);
-    BeatWork w{};
-    w.any = 0;
-    w.dead = 256;
-    w.fpb = w.dead + up(rows * 4);
-    w.norm = w.fpb + up((bpm_mode == LRA_BEAT_BPM_PER_FRAME ? cells : rows) * 8);
-    w.local = w.norm + up(cells * 8);
-    w.cum = w.local + up(cells * 8);
-    w.backlink = w.cum + up(cells * 8);
-    w.order = w.backlink + up(cells * 4);
-    w.total = w.order + up(cells * 4);
-    return w;
-}
-}  // namespace
-
-int64_t lra_beat_work_bytes(int64_t batch, int64_t n, int bpm_mode) { return beat_work_layout(batch, n, bpm_mode).total; }
-
-int lra_beat_exec(lra_ctx* ctx, const void* env, int64_t batch, int64_t n, int dtype, const void* bpm, int bpm_mode, double frame_rate, double tightness, int trim, void* out,
-                  void* work, int* any_nonzero) {
-    LRA_BIND(ctx);
-    if (any_nonzero) *any_nonzero = 0;
-    if (bpm_mode != LRA_BEAT_BPM_PER_ROW && bpm_mode != LRA_BEAT_BPM_PER_FRAME) return fail(LRA_EINVAL, "beat: unknown bpm mode");
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "beat: dtype must be LRA_F32 or LRA_F64");
-    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "beat: negative size");
-    if (!(tightness > 0)) return fail(LRA_EINVAL, "beat: tightness must be strictly positive");
-    if (!(frame_rate > 0)) return fail(LRA_EINVAL, "beat: frame_rate must be strictly positive");
-    if (batch == 0 || n == 0) return LRA_OK;
-    if (!env || !bpm || !out || !work) return fail(LRA_EINVAL, "null data pointer");
-    if (n > 0x7fffffffLL) return fail(LRA_EINVAL, "beat: too many frames per row");
-    const BeatWork w = beat_work_layout(batch, n, bpm_mode);
-    char* base = (char*)work;
-    beat::Args a{};
-    a.env = env;
-    a.n = n;
-    a.bpm = (const double*)bpm;
-    a.bpm_mode = bpm_mode;
-    a.frame_rate = frame_rate;
-    a.tightness = (float)tightness;
-    a.trim = trim != 0;
-    a.any = (int*)(base + w.any);
-    a.dead = (int*)(base + w.dead);
-    a.fpb = (double*)(base + w.fpb);
-    a.norm = base + w.norm;
-    a.local = base + w.local;
-    a.cum = (double*)(base + w.cum);
-    a.backlink = (int*)(base + w.backlink);
-    a.order = (int*)(base + w.order);
-    a.out = (unsigned char*)out;
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(beat::launch_beat(a, batch, dtype == LRA_F64, ctx->stream));
-    if (any_nonzero) {
-        int h = 0;
-        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *any_nonzero = h != 0;
-    }
-    return LRA_OK;
-}
-
-// ---- peak picking and onset backtracking (lra_peaks.h, launched from lra_peaks_inst.hip) ------------------------------------------------
-static_assert(peaks::kGreedy == LRA_PEAK_GREEDY && peaks::kDpCount == LRA_PEAK_DP_COUNT && peaks::kDpValue == LRA_PEAK_DP_VALUE, "peak codes");
-
-namespace {
-struct PeakWork {
-    int64_t status, norm, cand, values, taken, total;
-};
-PeakWork peak_work_layout(int64_t batch, int64_t n, int method) {
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t rows = batch > 0 ? batch : 0, len = n > 0 ? n : 0, cells = rows * len;
-    const bool dp = method != LRA_PEAK_GREEDY;
-    PeakWork w{};
-    w.status = 0;
-    w.norm = 256;
-    w.cand = w.norm + up(cells * 8);
-    w.values = w.cand + up(cells);
-    w.taken = w.values + up(dp ? rows * (len + 1) * 8 : 0);
-    w.total = w.taken + up(dp ? rows * ((len + 63) / 64) * 8 : 0);
-    return w;
-}
-}  // namespace
-
-int64_t lra_peak_pick_work_bytes(int64_t batch, int64_t n, int method) { return peak_work_layout(batch, n, method).total; }
-
-int lra_peak_pick_exec(lra_ctx* ctx, const void* x, int64_t batch, int64_t n, int dtype, int normalize, int64_t pre_max, int64_t post_max, int64_t pre_avg, int64_t post_avg,
-                       double delta, int64_t wait, int method, void* out, void* norm_out, void* work, int* status) {
-    LRA_BIND(ctx);
-    if (status) *status = 0;
-    if (method != LRA_PEAK_GREEDY && method != LRA_PEAK_DP_COUNT && method != LRA_PEAK_DP_VALUE) return fail(LRA_EINVAL, "peak_pick: unknown method");
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "peak_pick: dtype must be LRA_F32 or LRA_F64");
-    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "peak_pick: negative size");
-    if (pre_max < 0 || pre_avg < 0 || wait < 0 || !(delta >= 0)) return fail(LRA_EINVAL, "peak_pick: pre_max, pre_avg, delta and wait must be non-negative");
-    if (post_max <= 0 || post_avg <= 0) return fail(LRA_EINVAL, "peak_pick: post_max and post_avg must be positive");
-    if (batch == 0 || n == 0) {
-        if (status) *status = LRA_PEAK_ALL_FINITE;
-        return LRA_OK;
-    }
-    if (!x || !out || !work) return fail(LRA_EINVAL, "null data pointer");
-    if (n > 0x7fffffffLL - 64) return fail(LRA_EINVAL, "peak_pick: too many frames per row");
-    const PeakWork w = peak_work_layout(batch, n, method);
-    char* base = (char*)work;
-    peaks::Args a{};
-    a.x = x;
-    a.n = n;
-    a.normalize = normalize != 0;
-    a.pre_max = (int)peaks::clamp_window(pre_max, n);
-    a.post_max = (int)peaks::clamp_window(post_max, n);
-    a.pre_avg = (int)peaks::clamp_window(pre_avg, n);
-    a.post_avg = (int)peaks::clamp_window(post_avg, n);
-    a.wait = (int)peaks::clamp_window(wait, n);
-    a.delta = delta;
-    a.method = method;
-    a.status = (int*)(base + w.status);
-    a.norm = norm_out ? norm_out : base + w.norm;
-    a.cand = (unsigned char*)(base + w.cand);
-    a.values = (double*)(base + w.values);
-    a.taken = (unsigned long long*)(base + w.taken);
-    a.out = (unsigned char*)out;
-    LRA_HIP(hipMemsetAsync(work, 0, 2 * sizeof(int), ctx->stream));
-    LRA_HIP(peaks::launch_peak_pick(a, batch, dtype == LRA_F64, ctx->stream));
-    if (status) {
-        int h[2] = {0, 0};
-        LRA_HIP(hipMemcpyAsync(h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *status = (h[0] ? LRA_PEAK_ANY_NONZERO : 0) | (h[1] ? 0 : LRA_PEAK_ALL_FINITE);
-    }
-    return LRA_OK;
-}
-
-int lra_prev_minimum_exec(lra_ctx* ctx, const void* energy, int64_t batch, int64_t m, int dtype, void* out) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "prev_minimum: dtype must be LRA_F32 or LRA_F64");
-    if (batch < 0 || m < 0) return fail(LRA_EINVAL, "prev_minimum: negative size");
-    if (batch == 0 || m == 0) return LRA_OK;
-    if (!energy || !out) return fail(LRA_EINVAL, "null data pointer");
-    if (m > 0x7fffffffLL - 64) return fail(LRA_EINVAL, "prev_minimum: too many frames per row");
-    peaks::MinArgs a{energy, m, (int*)out};
-    LRA_HIP(peaks::launch_prev_minimum(a, batch, dtype == LRA_F64, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_chroma_exec(lra_ctx* ctx, const void* X, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
-                    const void* W, int64_t n_chroma, int norm, double threshold, int has_threshold, void* out, void* work, int* nonfinite) {
-    LRA_BIND(ctx);
-    if (nonfinite) *nonfinite = 0;
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "chroma: dtype must be LRA_F32 or LRA_F64");
-    if (norm != LRA_CHROMA_NORM_NONE && norm != LRA_CHROMA_NORM_L1 && norm != LRA_CHROMA_NORM_L2 && norm != LRA_CHROMA_NORM_INF) return fail(LRA_EINVAL, "chroma: unknown norm");
-    if (batch < 0 || n_bins < 0 || n_frames < 0 || n_chroma < 0) return fail(LRA_EINVAL, "chroma: negative size");
-    if (batch == 0 || n_frames == 0 || n_chroma == 0) return LRA_OK;
-    if (n_bins > 0x7fffffffLL || n_chroma > 0x7fffffffLL) return fail(LRA_EINVAL, "chroma: too many bins or rows");
-    if ((n_bins > 0 && (!X || !W)) || !out || !work) return fail(LRA_EINVAL, "null data pointer");
-    if (batch_stride < 0 || bin_stride < 0 || frame_stride < 0) return fail(LRA_EINVAL, "chroma: negative stride");
-    chroma::Args a{};
-    a.x = X;
-    a.batch_stride = batch_stride;
-    a.bin_stride = bin_stride;
-    a.frame_stride = frame_stride;
-    a.n_bins = (int)n_bins;
-    a.n_frames = n_frames;
-    a.w = W;
-    a.n_chroma = (int)n_chroma;
-    a.norm = norm;
-    a.has_thr = has_threshold != 0;
-    a.thr = threshold;
-    a.out = out;
-    a.flag = (int*)work;
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(chroma::launch_chroma(a, batch, dtype == LRA_F64, ctx->stream));
-    if (nonfinite) {
-        int h = 0;
-        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *nonfinite = h != 0;
-    }
-    return LRA_OK;
-}
-
-// ---- pitch tracking and tuning (lra_pitch.h, launched from lra_pitch_inst.hip) ------------------------------------------------------------
-static_assert(pitch::kRefMax == LRA_PITCH_REF_MAX && pitch::kRefRow == LRA_PITCH_REF_ROW && pitch::kRefScalar == LRA_PITCH_REF_SCALAR, "pitch ref codes");
-
-namespace {
-struct TuningWork {
-    int64_t state, hist, count, peak_pitch, peak_mag, total;
-    int cap;
-};
-TuningWork tuning_work_layout(int64_t batch, int64_t n_frames, int64_t masked_bins, int dtype) {
-    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
-    const int64_t frames = (batch > 0 ? batch : 0) * (n_frames > 0 ? n_frames : 0);
-    const int64_t es = dtype == LRA_F64 ? 8 : 4;
-    TuningWork w{};
-    w.cap = (int)(((masked_bins > 1 ? masked_bins : 1) + 1) / 2);
-    w.state = 0;
-    w.hist = 256;
-    w.count = w.hist + up(2 * pitch::kDigits * 8);
-    w.peak_pitch = w.count + up(frames * 4);
-    w.peak_mag = w.peak_pitch + up(frames * w.cap * es);
-    w.total = w.peak_mag + up(frames * w.cap * es);
-    return w;
-}
-
-// the checks lra_piptrack_exec and lra_tuning_exec share; fills what both kernels' forms read
-int pitch_args(pitch::Args& a, const void* S, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype, int64_t bin_lo,
-               int64_t bin_hi, int ref_mode, double threshold, const void* ref_row, double ref_scalar, double sr, int64_t n_fft) {
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "piptrack: dtype must be LRA_F32 or LRA_F64");
-    if (ref_mode != LRA_PITCH_REF_MAX && ref_mode != LRA_PITCH_REF_ROW && ref_mode != LRA_PITCH_REF_SCALAR) return fail(LRA_EINVAL, "piptrack: unknown ref mode");
-    if (batch < 0 || n_bins < 0 || n_frames < 0) return fail(LRA_EINVAL, "piptrack: negative size");
-    if (n_bins > 0x7fffffffLL - 64) return fail(LRA_EINVAL, "piptrack: too many bins");
-    if (batch_stride < 0 || bin_stride < 0 || frame_stride < 0) return fail(LRA_EINVAL, "piptrack: negative stride");
-    if (n_fft <= 0) return fail(LRA_EINVAL, "piptrack: n_fft must be positive");
-    if (batch > 0 && n_bins > 0 && n_frames > 0 && (!S || (ref_mode == LRA_PITCH_REF_ROW && !ref_row))) return fail(LRA_EINVAL, "null data pointer");
-    a.s = S;
-    a.batch_stride = batch_stride;
-    a.bin_stride = bin_stride;
-    a.frame_stride = frame_stride;
-    a.n_bins = (int)n_bins;
-    a.n_frames = n_frames;
-    a.lo = (int)(bin_lo < 0 ? 0 : (bin_lo > n_bins ? n_bins : bin_lo));
-    a.hi = (int)(bin_hi < 0 ? 0 : (bin_hi > n_bins ? n_bins : bin_hi));
-    a.ref_mode = ref_mode;
-    a.threshold = threshold;
-    a.ref_row = (const double*)ref_row;
-    a.ref_scalar = ref_scalar;
-    a.sr = sr;
-    a.n_fft = (double)n_fft;
-    return LRA_OK;
-}
-}  // namespace
-
-int lra_piptrack_exec(lra_ctx* ctx, const void* S, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
-                      int64_t bin_lo, int64_t bin_hi, int ref_mode, double threshold, const void* ref_row, double ref_scalar, double sr, int64_t n_fft, void* pitches, void* mags,
-                      int64_t out_batch_stride, int64_t out_bin_stride, int64_t out_frame_stride) {
-    LRA_BIND(ctx);
-    pitch::Args a{};
-    const int rc = pitch_args(a, S, batch, n_bins, n_frames, batch_stride, bin_stride, frame_stride, dtype, bin_lo, bin_hi, ref_mode, threshold, ref_row, ref_scalar, sr, n_fft);
-    if (rc != LRA_OK) return rc;
-    if (batch == 0 || n_bins == 0 || n_frames == 0) return LRA_OK;
-    if (!pitches || !mags) return fail(LRA_EINVAL, "null data pointer");
-    if (out_batch_stride < 0 || out_bin_stride < 0 || out_frame_stride < 0) return fail(LRA_EINVAL, "piptrack: negative stride");
-    a.pitches = pitches;
-    a.mags = mags;
-    a.out_batch_stride = out_batch_stride;
-    a.out_bin_stride = out_bin_stride;
-    a.out_frame_stride = out_frame_stride;
-    LRA_HIP(pitch::launch_piptrack(a, batch, false, dtype == LRA_F64, ctx->stream));
-    return LRA_OK;
-}
-
-int64_t lra_tuning_work_bytes(int64_t batch, int64_t n_frames, int64_t masked_bins, int dtype) { return tuning_work_layout(batch, n_frames, masked_bins, dtype).total; }
-
-int lra_tuning_exec(lra_ctx* ctx, const void* S, int64_t batch, int64_t n_bins, int64_t n_frames, int64_t batch_stride, int64_t bin_stride, int64_t frame_stride, int dtype,
-                    int64_t bin_lo, int64_t bin_hi, int ref_mode, double threshold, const void* ref_row, double ref_scalar, double sr, int64_t n_fft, const void* edges, int64_t n_hist,
-                    double bins_per_octave, void* work, void* out) {
-    LRA_BIND(ctx);
-    pitch::Args a{};
-    const int rc = pitch_args(a, S, batch, n_bins, n_frames, batch_stride, bin_stride, frame_stride, dtype, bin_lo, bin_hi, ref_mode, threshold, ref_row, ref_scalar, sr, n_fft);
-    if (rc != LRA_OK) return rc;
-    if (n_hist <= 0 || n_hist > 0x7fffffffLL - 2) return fail(LRA_EINVAL, "tuning: the histogram needs between 1 and 2^31 - 3 bins");
-    if (!edges || !work || !out) return fail(LRA_EINVAL, "null data pointer");
-    const TuningWork w = tuning_work_layout(batch, n_frames, a.hi - a.lo, dtype);
-    char* base = (char*)work;
-    LRA_HIP(hipMemsetAsync(out, 0, (size_t)(n_hist + 2) * 8, ctx->stream));
-    if (batch == 0 || n_bins == 0 || n_frames == 0) return LRA_OK;
-    LRA_HIP(hipMemsetAsync(work, 0, (size_t)w.count, ctx->stream));  // the select's state and histogram
-    a.peak_pitch = base + w.peak_pitch;
-    a.peak_mag = base + w.peak_mag;
-    a.peak_count = (int*)(base + w.count);
-    a.cap = w.cap;
-    const bool f64 = dtype == LRA_F64;
-    LRA_HIP(pitch::launch_piptrack(a, batch, true, f64, ctx->stream));
-    pitch::SelectState* state = (pitch::SelectState*)(base + w.state);
-    pitch::SelectArgs sel{a.peak_mag, a.peak_count, batch * n_frames, w.cap, (unsigned long long*)(base + w.hist), state};
-    LRA_HIP(pitch::launch_median(sel, f64, ctx->stream));
-    pitch::HistArgs h{a.peak_pitch, a.peak_mag, a.peak_count, batch * n_frames, batch * n_frames * w.cap, w.cap, state, (const double*)edges, (int)n_hist, bins_per_octave,
-                      (unsigned long long*)out};
-    LRA_HIP(pitch::launch_tuning_hist(h, f64, ctx->stream));
-    LRA_HIP(hipMemcpyAsync((char*)out + (size_t)(n_hist + 1) * 8, &state->total, 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_pitch_tuning_exec(lra_ctx* ctx, const void* freq, int64_t n, int dtype, const void* edges, int64_t n_hist, double bins_per_octave, void* out) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "pitch_tuning: dtype must be LRA_F32 or LRA_F64");
-    if (n < 0) return fail(LRA_EINVAL, "pitch_tuning: negative size");
-    if (n_hist <= 0 || n_hist > 0x7fffffffLL - 2) return fail(LRA_EINVAL, "pitch_tuning: the histogram needs between 1 and 2^31 - 3 bins");
-    if (!edges || !out || (n > 0 && !freq)) return fail(LRA_EINVAL, "null data pointer");
-    LRA_HIP(hipMemsetAsync(out, 0, (size_t)(n_hist + 2) * 8, ctx->stream));
-    const int64_t n_segments = (n + pitch::kPlainSeg - 1) / pitch::kPlainSeg;
-    pitch::HistArgs h{freq, nullptr, nullptr, n_segments, n, pitch::kPlainSeg, nullptr, (const double*)edges, (int)n_hist, bins_per_octave, (unsigned long long*)out};
-    LRA_HIP(pitch::launch_tuning_hist(h, dtype == LRA_F64, ctx->stream));
-    return LRA_OK;
-}
-
-// ---- sequence.viterbi and its variants (lra_viterbi.h, launched from lra_viterbi_inst.hip) -------------------------------------------------
-static_assert(viterbi::kGenerative == LRA_VITERBI_GENERATIVE && viterbi::kDiscriminative == LRA_VITERBI_DISCRIMINATIVE && viterbi::kBinary == LRA_VITERBI_BINARY &&
-                  viterbi::kLog == LRA_VITERBI_LOG,
-              "viterbi kinds");
-static_assert(viterbi::kFlagNegative == LRA_VITERBI_FLAG_NEGATIVE && viterbi::kFlagAboveOne == LRA_VITERBI_FLAG_ABOVE_ONE && viterbi::kFlagColumnSum == LRA_VITERBI_FLAG_COLUMN_SUM,
-              "viterbi flags");
-static_assert(viterbi::kMaxStates == LRA_VITERBI_MAX_STATES && viterbi::kSmallMax == LRA_VITERBI_SMALL_MAX && viterbi::kLdsMax == LRA_VITERBI_LDS_MAX, "viterbi limits");
-static_assert(viterbi::geometry(viterbi::kMaxStates, 0).lds <= viterbi::kLdsMax && viterbi::geometry(viterbi::kMaxStates, 1).lds <= viterbi::kLdsMax, "viterbi: the largest call fits");
-
-int64_t lra_viterbi_lds_bytes(int n_states, int n_pred) {
-    if (n_states < 1) return 0;
-    if (n_states > viterbi::kMaxStates) return (int64_t)viterbi::kLdsMax + 16LL * (n_states - viterbi::kMaxStates);  // (refused: the limit is a round number below what the LDS holds)
-    return viterbi::geometry(n_states, n_pred > 0 ? n_pred : 0).lds;
-}
-
-int lra_viterbi_prep_exec(lra_ctx* ctx, const void* prob, int dtype, int kind, int64_t chains, int n_states, int64_t n_steps, double eps, const void* log_marginal, int n_labels,
-                          void* log_prob, void* work, int* flags) {
-    LRA_BIND(ctx);
-    if (flags) *flags = 0;
-    if (kind < LRA_VITERBI_GENERATIVE || kind > LRA_VITERBI_LOG) return fail(LRA_EINVAL, "viterbi: unknown kind");
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "viterbi: dtype must be LRA_F32 or LRA_F64");
-    if (chains < 0 || n_steps < 0 || n_states < 1) return fail(LRA_EINVAL, "viterbi: negative size");
-    if (kind == LRA_VITERBI_BINARY && (n_states != 2 || n_labels < 1)) return fail(LRA_EINVAL, "viterbi: a binary chain has 2 states and at least one label");
-    if (chains == 0 || n_steps == 0) return LRA_OK;
-    if (!prob || !log_prob || !work) return fail(LRA_EINVAL, "null data pointer");
-    if ((kind == LRA_VITERBI_DISCRIMINATIVE || kind == LRA_VITERBI_BINARY) && !log_marginal) return fail(LRA_EINVAL, "viterbi: log_marginal is missing");
-    viterbi::PrepArgs a{};
-    a.prob = prob;
-    a.f64 = dtype == LRA_F64;
-    a.kind = kind;
-    a.clips = chains;
-    a.S = n_states;
-    a.T = n_steps;
-    a.eps = eps;
-    a.log_marginal = (const double*)log_marginal;
-    a.n_labels = n_labels > 0 ? n_labels : 1;
-    a.log_prob = (double*)log_prob;
-    a.flags = (int*)work;
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(viterbi::launch_prep(a, ctx->stream));
-    if (flags) {
-        int h = 0;
-        LRA_HIP(hipMemcpyAsync(&h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *flags = h;
-    }
-    return LRA_OK;
-}
-
-int lra_viterbi_exec(lra_ctx* ctx, const void* log_prob, int64_t chains, int n_states, int64_t n_steps, const void* log_trans, const void* log_p_init, int n_tables, double threshold,
-                     int n_pred, const void* pred_k, const void* pred_lt, const void* pred_n, void* ptr, void* states, void* logp) {
-    LRA_BIND(ctx);
-    if (chains < 0 || n_steps < 1 || n_states < 1 || n_tables < 1 || n_pred < 0) return fail(LRA_EINVAL, "viterbi: need n_states, n_steps and n_tables of at least 1");
-    if (n_states > viterbi::kMaxStates)
-        return fail(LRA_EINVAL, "viterbi: n_states=" + std::to_string(n_states) + " does not fit the LDS of a workgroup (at most " + std::to_string(viterbi::kMaxStates) + ")");
-    if (threshold != threshold) return fail(LRA_EINVAL, "viterbi: threshold is NaN");
-    const bool small = n_states <= viterbi::kSmallMax, listed = !small && threshold > -HUGE_VAL;
-    if (!small && n_tables != 1) return fail(LRA_EINVAL, "viterbi: a table per chain is served up to " + std::to_string(viterbi::kSmallMax) + " states");
-    if (listed && (n_pred < 1 || n_pred > n_states)) return fail(LRA_EINVAL, "viterbi: a thresholded search needs predecessor lists of 1 to n_states rows");
-    if (chains == 0) return LRA_OK;
-    if (!log_prob || !log_p_init || !ptr || !states || !logp || (!listed && !log_trans) || (listed && (!pred_k || !pred_lt || !pred_n))) return fail(LRA_EINVAL, "null data pointer");
-    viterbi::Args a{};
-    a.log_prob = (const double*)log_prob;
-    a.log_trans = (const double*)log_trans;
-    a.log_p_init = (const double*)log_p_init;
-    a.n_tables = n_tables;
-    a.chains = chains;
-    a.S = n_states;
-    a.T = n_steps;
-    a.threshold = threshold;
-    a.n_pred = listed ? n_pred : 0;
-    a.pred_k = (const uint16_t*)pred_k;
-    a.pred_lt = (const double*)pred_lt;
-    a.pred_n = (const int*)pred_n;
-    a.ptr = (uint16_t*)ptr;
-    a.states = (uint16_t*)states;
-    a.logp = (double*)logp;
-    a.g = viterbi::geometry(n_states, a.n_pred);
-    LRA_HIP(viterbi::launch_decode(a, ctx->stream));
-    return LRA_OK;
-}
-
-// ---- sequence.dtw and dtw_backtracking (lra_dtw.h, launched from lra_dtw_inst.hip) ---------------------------------------------------------
-static_assert(dtw::kEuclidean == LRA_DTW_EUCLIDEAN && dtw::kSqeuclidean == LRA_DTW_SQEUCLIDEAN && dtw::kCityblock == LRA_DTW_CITYBLOCK && dtw::kCosine == LRA_DTW_COSINE, "dtw metrics");
-static_assert(dtw::kF32 == LRA_F32 && dtw::kF64 == LRA_F64 && dtw::kI32 == LRA_DTW_I32 && dtw::kI64 == LRA_DTW_I64 && dtw::kU8 == LRA_DTW_U8, "dtw types");
-static_assert(dtw::kFlagNan == LRA_DTW_FLAG_NAN && dtw::kFlagEndInf == LRA_DTW_FLAG_END_INF && dtw::kFlagRowInf == LRA_DTW_FLAG_ROW_INF &&
-                  dtw::kFlagNotOrigin == LRA_DTW_FLAG_NOT_ORIGIN && dtw::kFlagBadStep == LRA_DTW_FLAG_BAD_STEP,
-              "dtw flags");
-static_assert(dtw::kMaxSteps == LRA_DTW_MAX_STEPS && dtw::kMaxStep == LRA_DTW_MAX_STEP && dtw::kStartEnd == LRA_DTW_START_END && dtw::kStartArgmin == LRA_DTW_START_ARGMIN, "dtw limits");
-static_assert(dtw::geometry(64, dtw::kMaxStep, dtw::kMaxStep).lds <= dtw::kLdsMax, "dtw: the largest tile with the widest halo fits");
-
-int64_t lra_dtw_lds_bytes(int tile, int max_0, int max_1) {
-    if ((tile != 0 && !dtw::tile_ok(tile)) || max_0 < 0 || max_1 < 0 || max_0 > dtw::kMaxStep || max_1 > dtw::kMaxStep) return 0;
-    return dtw::geometry(tile, max_0, max_1).lds;
-}
-
-// the step table of a call (host arrays) as the kernels take it; false where it breaks a limit
-static bool dtw_step_table(const int32_t* steps, const double* w_add, const double* w_mul, int n_steps, dtw::StepTable* st, std::string* why) {
-    if (!steps || n_steps < 1 || n_steps > dtw::kMaxSteps) {
-        *why = "dtw: the step table holds 1 to " + std::to_string(dtw::kMaxSteps) + " steps";
-        return false;
-    }
-    *st = dtw::StepTable{};
-    st->n = n_steps;
-    for (int i = 0; i < n_steps; ++i) {
-        const int s0 = steps[2 * i], s1 = steps[2 * i + 1];
-        if (s0 < 0 || s1 < 0 || s0 > dtw::kMaxStep || s1 > dtw::kMaxStep || (s0 == 0 && s1 == 0)) {
-            *why = "dtw: a step component lies in 0 .. " + std::to_string(dtw::kMaxStep) + " and no step is (0, 0)";
-            return false;
-        }
-        st->s0[i] = s0;
-        st->s1[i] = s1;
-        st->w_add[i] = w_add ? w_add[i] : 0.0;
-        st->w_mul[i] = w_mul ? w_mul[i] : 1.0;
-        if (s0 > st->max0) st->max0 = s0;
-        if (s1 > st->max1) st->max1 = s1;
-    }
-    return true;
-}
-
-// the flag word of a stage, read back (this waits for the stream)
-static int dtw_read_flags(lra_ctx* ctx, const void* work, int* flags) {
-    int h = 0;
-    LRA_HIP(hipMemcpyAsync(&h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    LRA_HIP(hipStreamSynchronize(ctx->stream));
-    *flags = h;
-    return LRA_OK;
-}
-
-int lra_dtw_cost_exec(lra_ctx* ctx, const void* X, const void* Y, int dtype, int64_t n_features, int64_t N, int64_t M, int metric, void* C, void* work, int* flags) {
-    LRA_BIND(ctx);
-    if (flags) *flags = 0;
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "dtw: the features must be LRA_F32 or LRA_F64");
-    if (metric < LRA_DTW_EUCLIDEAN || metric > LRA_DTW_COSINE) return fail(LRA_EINVAL, "dtw: unknown metric");
-    if (n_features < 1 || N < 1 || M < 1) return fail(LRA_EINVAL, "dtw: need at least one feature and one frame of each sequence");
-    if (!X || !Y || !C || !work) return fail(LRA_EINVAL, "null data pointer");
-    dtw::CostArgs a{X, Y, dtype == LRA_F64, metric, n_features, N, M, (double*)C, (int*)work};
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(dtw::launch_cost(a, ctx->stream));
-    return flags ? dtw_read_flags(ctx, work, flags) : LRA_OK;
-}
-
-int lra_dtw_prepare_exec(lra_ctx* ctx, const void* C, int dtype, int64_t count, void* out, void* work, int* flags) {
-    LRA_BIND(ctx);
-    if (flags) *flags = 0;
-    if (dtype != LRA_F32 && dtype != LRA_F64 && dtype != LRA_DTW_I32 && dtype != LRA_DTW_I64 && dtype != LRA_DTW_U8) return fail(LRA_EINVAL, "dtw: unknown type of C");
-    if (count < 1) return fail(LRA_EINVAL, "dtw: C is empty");
-    if (!C || !work || (!out && dtype != LRA_F64)) return fail(LRA_EINVAL, "null data pointer");
-    dtw::PrepArgs a{C, dtype, count, (double*)out, (int*)work};
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(int), ctx->stream));
-    LRA_HIP(dtw::launch_prepare(a, ctx->stream));
-    return flags ? dtw_read_flags(ctx, work, flags) : LRA_OK;
-}
-
-int lra_dtw_accumulate_exec(lra_ctx* ctx, const void* C, int64_t N, int64_t M, const int32_t* steps, const double* weights_add, const double* weights_mul, int n_steps, int subseq, int band,
-                            int64_t band_lo, int64_t band_hi, int tile, void* D, void* step_idx) {
-    LRA_BIND(ctx);
-    if (N < 1 || M < 1) return fail(LRA_EINVAL, "dtw: C is empty");
-    if (tile != 0 && !dtw::tile_ok(tile)) return fail(LRA_EINVAL, "dtw: tile is 0 (the library's choice), 8, 16, 32 or 64");
-    if (!C || !D || !step_idx) return fail(LRA_EINVAL, "null data pointer");
-    dtw::AccArgs a{};
-    std::string why;
-    if (!dtw_step_table(steps, weights_add, weights_mul, n_steps, &a.st, &why)) return fail(LRA_EINVAL, why);
-    a.C = (const double*)C;
-    a.N = N;
-    a.M = M;
-    a.subseq = subseq != 0;
-    a.band = band != 0;
-    a.band_lo = band_lo;
-    a.band_hi = band_hi;
-    a.D = (double*)D;
-    a.steps = (uint8_t*)step_idx;
-    LRA_HIP(dtw::launch_accumulate(a, tile, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_dtw_widen_exec(lra_ctx* ctx, const void* step_idx, int64_t count, void* out) {
-    LRA_BIND(ctx);
-    if (count < 0) return fail(LRA_EINVAL, "dtw: negative size");
-    if (count == 0) return LRA_OK;
-    if (!step_idx || !out) return fail(LRA_EINVAL, "null data pointer");
-    LRA_HIP(dtw::launch_widen(dtw::WidenArgs{(const uint8_t*)step_idx, count, (int*)out}, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_dtw_backtrack_exec(lra_ctx* ctx, const void* D, const void* step_idx, int steps_i32, int64_t N, int64_t M, const int32_t* steps, int n_steps, int subseq, int64_t start, void* path,
-                           void* work, int64_t* length, int* status) {
-    LRA_BIND(ctx);
-    if (N < 1 || M < 1) return fail(LRA_EINVAL, "dtw: the step matrix is empty");
-    if (!step_idx || !path || !work || !length || !status) return fail(LRA_EINVAL, "null data pointer");
-    if (start < LRA_DTW_START_ARGMIN || start >= M) return fail(LRA_EINVAL, "dtw: start is a column of the matrix, LRA_DTW_START_END or LRA_DTW_START_ARGMIN");
-    if (start == LRA_DTW_START_ARGMIN && !D) return fail(LRA_EINVAL, "dtw: LRA_DTW_START_ARGMIN needs D");
-    dtw::BackArgs a{};
-    std::string why;
-    if (!dtw_step_table(steps, nullptr, nullptr, n_steps, &a.st, &why)) return fail(LRA_EINVAL, why);
-    a.D = (const double*)D;
-    a.steps = step_idx;
-    a.steps_i32 = steps_i32 != 0;
-    a.N = N;
-    a.M = M;
-    a.subseq = subseq != 0;
-    a.start = start;
-    a.path = (long long*)path;
-    a.cap = N + M - 1;
-    a.length = (long long*)work;
-    a.status = (int*)((char*)work + 8);
-    LRA_HIP(dtw::launch_backtrack(a, ctx->stream));
-    struct { long long length; int status; int pad; } h{};
-    LRA_HIP(hipMemcpyAsync(&h, work, 16, hipMemcpyDeviceToHost, ctx->stream));
-    LRA_HIP(hipStreamSynchronize(ctx->stream));
-    *length = h.length;
-    *status = h.status;
-    return LRA_OK;
-}
-
-// ---- sequence.rqa (lra_rqa.h, launched from lra_rqa_inst.hip) -----------------------------------------------------------------------------
-static_assert(rqa::kF32 == LRA_F32 && rqa::kF64 == LRA_F64, "rqa types");
-static_assert(rqa::kWorkBytes == LRA_RQA_WORK_BYTES, "rqa work area");
-static_assert(rqa::geometry(64, 1024).iters <= rqa::kMaxIters && rqa::geometry(64, 1024).lds <= 64 * 1024, "rqa: the largest geometry fits");
-
-int64_t lra_rqa_lds_bytes(int rows, int strip) {
-    if ((rows != 0 && !rqa::rows_ok(rows)) || (strip != 0 && !rqa::strip_ok(strip))) return 0;
-    return rqa::geometry(rows, strip).lds;
-}
-
-int lra_rqa_score_exec(lra_ctx* ctx, const void* sim, int dtype, int64_t N, int64_t M, double gap_onset, double gap_extend, int knight_moves, int rows, int strip, void* score,
-                       void* pointers) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "rqa: sim must be LRA_F32 or LRA_F64");
-    if (N < 1 || M < 1) return fail(LRA_EINVAL, "rqa: sim is empty");
-    if (lra_rqa_lds_bytes(rows, strip) == 0) return fail(LRA_EINVAL, "rqa: rows is 0 (the library's choice) or a power of two up to 64, strip 0 or a power of two from 4 to 1024");
-    if (!sim || !score || !pointers) return fail(LRA_EINVAL, "null data pointer");
-    rqa::ScoreArgs a{};
-    a.sim = sim;
-    a.f64 = dtype == LRA_F64;
-    a.N = N;
-    a.M = M;
-    a.gap_onset = gap_onset;
-    a.gap_extend = gap_extend;
-    a.knight = knight_moves != 0;
-    a.score = score;
-    a.ptr = (int8_t*)pointers;
-    LRA_HIP(rqa::launch_score(a, rows, strip, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_rqa_argmax_exec(lra_ctx* ctx, const void* score, int dtype, int64_t count, void* work) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "rqa: score must be LRA_F32 or LRA_F64");
-    if (count < 1) return fail(LRA_EINVAL, "rqa: score is empty");
-    if (!score || !work) return fail(LRA_EINVAL, "null data pointer");
-    rqa::ArgmaxArgs a{};
-    a.score = score;
-    a.f64 = dtype == LRA_F64;
-    a.count = count;
-    a.out = (long long*)work;
-    a.part_i = (long long*)((char*)work + 16);
-    a.part_v = (double*)((char*)work + 16 + 8 * rqa::kMaxParts);
-    LRA_HIP(rqa::launch_argmax(a, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_rqa_backtrack_exec(lra_ctx* ctx, const void* pointers, int64_t N, int64_t M, void* work, void* path, int64_t* length) {
-    LRA_BIND(ctx);
-    if (N < 1 || M < 1) return fail(LRA_EINVAL, "rqa: the pointer matrix is empty");
-    if (!pointers || !work || !path || !length) return fail(LRA_EINVAL, "null data pointer");
-    rqa::BackArgs a{};
-    a.ptr = (const int8_t*)pointers;
-    a.N = N;
-    a.M = M;
-    a.start = (const long long*)work;
-    a.path = (unsigned long long*)path;
-    a.cap = N < M ? N : M;
-    a.length = (long long*)((char*)work + 8);
-    LRA_HIP(rqa::launch_backtrack(a, ctx->stream));
-    long long h = 0;
-    LRA_HIP(hipMemcpyAsync(&h, (char*)work + 8, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    LRA_HIP(hipStreamSynchronize(ctx->stream));
-    *length = h;
-    return LRA_OK;
-}
-
-// ---- segment.cross_similarity and recurrence_matrix (lra_knn.h, launched from lra_knn_inst.hip) -------------------------------------------
-static_assert(knn::kMaxK == LRA_KNN_MAX_K && knn::kWorkBytes == LRA_KNN_WORK_BYTES, "knn limits");
-static_assert(knn::kConnectivity == LRA_KNN_CONNECTIVITY && knn::kDistance == LRA_KNN_DISTANCE && knn::kAffinity == LRA_KNN_AFFINITY, "knn modes");
-static_assert(knn::kBwScalar == LRA_KNN_BW_SCALAR && knn::kBwMeanK == LRA_KNN_BW_MEAN_K && knn::kBwGmeanK == LRA_KNN_BW_GMEAN_K && knn::kBwMeanKAvg == LRA_KNN_BW_MEAN_K_AVG &&
-                  knn::kBwGmeanKAvg == LRA_KNN_BW_GMEAN_K_AVG && knn::kBwMeanKAvgPair == LRA_KNN_BW_MEAN_K_AVG_AND_PAIR && knn::kBwMatrix == LRA_KNN_BW_MATRIX,
-              "knn bandwidth modes");
-static_assert(knn::kStatusEmptyGraph == LRA_KNN_STATUS_EMPTY_GRAPH && knn::kStatusRowEmpty == LRA_KNN_STATUS_ROW_EMPTY && knn::kStatusNonPositive == LRA_KNN_STATUS_NON_POSITIVE,
-              "knn status bits");
-static_assert(knn::geometry(0, 0, 1024).lds > 0 && knn::geometry(0, 0, knn::kMaxK).lds > 0 && knn::geometry(0, 0, knn::kMaxK).lds <= knn::kLdsMax, "knn: the longest list is served");
-
-int64_t lra_knn_lds_bytes(int rows, int tile, int k) { return knn::geometry(rows, tile, k).lds; }
-
-// the work area: the status word, the lowest empty row, the scalar bandwidth, the entry count
-struct KnnWork {
-    int status, first_empty;
-    double bandwidth;
-    long long total;
-};
-static_assert(sizeof(KnnWork) <= LRA_KNN_WORK_BYTES, "knn work area");
-
-static bool knn_fill_value(knn::Value* v, int mode, int bw_mode, double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, int64_t m, void* work, std::string* why) {
-    if (mode < LRA_KNN_CONNECTIVITY || mode > LRA_KNN_AFFINITY) return *why = "knn: unknown mode", false;
-    if (bw_mode < LRA_KNN_BW_SCALAR || bw_mode > LRA_KNN_BW_MATRIX) return *why = "knn: unknown bandwidth mode", false;
-    v->mode = mode;
-    v->bw_mode = bw_mode;
-    v->bw_scalar = bw_scalar;
-    v->bw_ptr = bw_on_device ? &((const KnnWork*)work)->bandwidth : nullptr;
-    v->sigma = (const double*)sigma;
-    v->matrix = (const double*)matrix;
-    v->m = m;
-    if (mode == LRA_KNN_AFFINITY) {
-        if (bw_mode == LRA_KNN_BW_MATRIX ? !matrix : (bw_mode != LRA_KNN_BW_SCALAR && !sigma)) return *why = "knn: the bandwidth mode's table is missing", false;
-        if (bw_on_device && !work) return *why = "null data pointer", false;
-    }
-    return true;
-}
-
-int lra_knn_select_exec(lra_ctx* ctx, const void* Q, const void* R, int dtype, int64_t n_features, int64_t n, int64_t m, int metric, int k, int64_t width, int skip_zero, int rows, int tile,
-                        void* count, void* index, void* distance) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "knn: the features must be LRA_F32 or LRA_F64");
-    if (metric < LRA_DTW_EUCLIDEAN || metric > LRA_DTW_COSINE) return fail(LRA_EINVAL, "knn: unknown metric");
-    if (n_features < 1 || n < 1 || m < 1) return fail(LRA_EINVAL, "knn: need at least one feature and one frame of each sequence");
-    if (n > 0x7fffffffLL || m > 0x7fffffffLL) return fail(LRA_EINVAL, "knn: too many frames");
-    if (k < 1 || k > LRA_KNN_MAX_K) return fail(LRA_EINVAL, "knn: k must be between 1 and LRA_KNN_MAX_K = " + std::to_string(LRA_KNN_MAX_K));
-    if (width < 0) return fail(LRA_EINVAL, "knn: negative width");
-    if (lra_knn_lds_bytes(rows, tile, k) == 0)
-        return fail(LRA_EINVAL, "knn: rows is 0 (the library's choice) or a power of two up to 16, tile 0 or a power of two from 4 to 1024, rows * tile at most 2048, and the lists must fit the LDS");
-    if (!Q || !R || !count || !index || !distance) return fail(LRA_EINVAL, "null data pointer");
-    knn::SelectArgs a{};
-    a.Q = Q;
-    a.R = R;
-    a.f64 = dtype == LRA_F64;
-    a.metric = metric;
-    a.d = n_features;
-    a.n = n;
-    a.m = m;
-    a.k = k;
-    a.width = width;
-    a.skip_zero = skip_zero != 0;
-    a.cnt = (int*)count;
-    a.idx = (int*)index;
-    a.dist = (double*)distance;
-    LRA_HIP(knn::launch_select(a, rows, tile, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_knn_mutual_exec(lra_ctx* ctx, int64_t n, int k, const void* count, const void* index, const void* distance, int sym, int drop_zero, void* keep) {
-    LRA_BIND(ctx);
-    if (n < 1 || k < 1) return fail(LRA_EINVAL, "knn: the lists are empty");
-    if (!count || !index || !distance || !keep) return fail(LRA_EINVAL, "null data pointer");
-    LRA_HIP(knn::launch_mutual(knn::MutualArgs{n, k, (const int*)count, (const int*)index, (const double*)distance, sym != 0, drop_zero != 0, (uint8_t*)keep}, ctx->stream));
-    return LRA_OK;
-}
-
-// the status word and the lowest empty row, read back (this waits for the stream)
-static int knn_read_status(lra_ctx* ctx, const void* work, int* status, int64_t* first_empty) {
-    KnnWork h{};
-    LRA_HIP(hipMemcpyAsync(&h, work, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    LRA_HIP(hipStreamSynchronize(ctx->stream));
-    *status = h.status;
-    if (first_empty) *first_empty = h.first_empty;
-    return LRA_OK;
-}
-
-int lra_knn_bandwidth_exec(lra_ctx* ctx, int64_t n, int k, const void* count, const void* distance, const void* keep, int add_self, int bandwidth_k, int median, void* dist_to_k, void* avg,
-                           void* work, int* status, int64_t* first_empty) {
-    LRA_BIND(ctx);
-    if (n < 1 || k < 1 || bandwidth_k < 1) return fail(LRA_EINVAL, "knn: the lists are empty, or bandwidth_k is not positive");
-    if (n > 0x7fffffffLL) return fail(LRA_EINVAL, "knn: too many frames");
-    if (!count || !distance || !dist_to_k || !avg || !work || !status || !first_empty) return fail(LRA_EINVAL, "null data pointer");
-    const KnnWork init{0, 0x7fffffff, 0.0, 0};
-    LRA_HIP(hipMemcpyAsync(work, &init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-    LRA_HIP(hipStreamSynchronize(ctx->stream));   // (init lives on this frame)
-    KnnWork* w = (KnnWork*)work;
-    knn::BandwidthArgs a{n, k, (const int*)count, (const double*)distance, (const uint8_t*)keep, add_self != 0, bandwidth_k, (double*)dist_to_k, (double*)avg, &w->status};
-    LRA_HIP(knn::launch_bandwidth(a, median ? &w->bandwidth : nullptr, ctx->stream));
-    return knn_read_status(ctx, work, status, first_empty);
-}
-
-int lra_knn_bw_check_exec(lra_ctx* ctx, const void* matrix, int64_t count, void* work, int* status) {
-    LRA_BIND(ctx);
-    if (count < 1) return fail(LRA_EINVAL, "knn: the bandwidth matrix is empty");
-    if (!matrix || !work || !status) return fail(LRA_EINVAL, "null data pointer");
-    LRA_HIP(hipMemsetAsync(work, 0, sizeof(KnnWork), ctx->stream));
-    LRA_HIP(knn::launch_bw_check(knn::CheckArgs{(const double*)matrix, count, &((KnnWork*)work)->status}, ctx->stream));
-    return knn_read_status(ctx, work, status, nullptr);
-}
-
-int lra_knn_emit_exec(lra_ctx* ctx, int64_t n, int64_t m, int k, const void* count, const void* index, const void* distance, const void* keep, int self, int mode, int bw_mode,
-                      double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, void* work, void* counts, void* indptr, void* indices, void* data, void* dense,
-                      int64_t* total) {
-    LRA_BIND(ctx);
-    if (n < 1 || m < 1 || k < 1) return fail(LRA_EINVAL, "knn: the lists are empty");
-    if (n * ((int64_t)k + 1) > 0x7fffffffLL) return fail(LRA_EINVAL, "knn: more entries than an int32 index array addresses");
-    if (!count || !index || !distance || !keep || !work) return fail(LRA_EINVAL, "null data pointer");
-    if (dense ? false : (!counts || !indptr || !indices || !data || !total)) return fail(LRA_EINVAL, "null data pointer");
-    knn::EmitArgs a{};
-    std::string why;
-    if (!knn_fill_value(&a.val, mode, bw_mode, bw_scalar, bw_on_device, sigma, matrix, m, work, &why)) return fail(LRA_EINVAL, why);
-    a.n = n;
-    a.m = m;
-    a.k = k;
-    a.cnt = (const int*)count;
-    a.idx = (const int*)index;
-    a.dist = (const double*)distance;
-    a.keep = (const uint8_t*)keep;
-    a.self = self != 0;
-    a.counts = (int*)counts;
-    a.indptr = dense ? nullptr : (int*)indptr;
-    a.indices = (int*)indices;
-    a.data = data;
-    a.dense = dense;
-    a.total = &((KnnWork*)work)->total;
-    if (dense) LRA_HIP(hipMemsetAsync(dense, 0, (size_t)n * (size_t)m * (mode == LRA_KNN_CONNECTIVITY ? 1 : 8), ctx->stream));
-    LRA_HIP(knn::launch_emit(a, ctx->stream));
-    if (!dense) {
-        long long h = 0;
-        LRA_HIP(hipMemcpyAsync(&h, a.total, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        LRA_HIP(hipStreamSynchronize(ctx->stream));
-        *total = h;
-    }
-    return LRA_OK;
-}
-
-int lra_knn_dense_exec(lra_ctx* ctx, const void* Q, const void* R, int dtype, int64_t n_features, int64_t n, int64_t m, int metric, int64_t width, int self, int mode, int bw_mode,
-                       double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, void* work, void* out) {
-    LRA_BIND(ctx);
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "knn: the features must be LRA_F32 or LRA_F64");
-    if (metric < LRA_DTW_EUCLIDEAN || metric > LRA_DTW_COSINE) return fail(LRA_EINVAL, "knn: unknown metric");
-    if (n_features < 1 || n < 1 || m < 1) return fail(LRA_EINVAL, "knn: need at least one feature and one frame of each sequence");
-    if (width < 0) return fail(LRA_EINVAL, "knn: negative width");
-    if (!Q || !R || !out) return fail(LRA_EINVAL, "null data pointer");
-    knn::DenseArgs a{};
-    std::string why;
-    if (!knn_fill_value(&a.val, mode, bw_mode, bw_scalar, bw_on_device, sigma, matrix, m, work, &why)) return fail(LRA_EINVAL, why);
-    a.Q = Q;
-    a.R = R;
-    a.f64 = dtype == LRA_F64;
-    a.metric = metric;
-    a.d = n_features;
-    a.n = n;
-    a.m = m;
-    a.width = width;
-    a.self = self != 0;
-    a.out = out;
-    LRA_HIP(knn::launch_dense(a, ctx->stream));
-    return LRA_OK;
-}
-
-// ---- yin and the front half of pyin (lra_yin.h, launched from lra_yin_inst.hip) ----------------------------------------------------------
-static_assert(yin::kF0 == LRA_YIN_F0 && yin::kFrames == LRA_YIN_FRAMES, "yin codes");
-static_assert(yin::transform_length(64, 27) == 160 && yin::transform_length(2048, 340) == 2400 && yin::transform_length(2048, 2047) == 4800 && yin::transform_length(4096, 705) == 0,
-              "yin transform lengths");
-
-int64_t lra_yin_lds_bytes(int frame_length, int max_period) {
-    if (frame_length < 1 || max_period < 1) return 0;
-    return yin::lds_layout(yin::transform_length(frame_length, max_period), max_period).total;
-}
-
-int lra_yin_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, int dtype, int frame_length, int hop_length, int center, int pad_mode, int min_period, int max_period,
-                 double trough_threshold, double sr, int mode, void* f0, void* frames, void* shifts) {
-    LRA_BIND(ctx);
-    if (mode != LRA_YIN_F0 && mode != LRA_YIN_FRAMES) return fail(LRA_EINVAL, "yin: unknown mode");
-    if (dtype != LRA_F32 && dtype != LRA_F64) return fail(LRA_EINVAL, "yin: dtype must be LRA_F32 or LRA_F64");
-    if (frame_length < 3 || hop_length < 1) return fail(LRA_EINVAL, "yin: frame_length must be at least 3 and hop_length positive");
-    if (pad_mode < 0 || pad_mode > 3) return fail(LRA_EINVAL, "yin: unknown pad mode");
-    if (min_period < 1 || max_period <= min_period || max_period > frame_length - 1) return fail(LRA_EINVAL, "yin: need 1 <= min_period < max_period <= frame_length - 1");
-    if (batch < 0 || n < 0) return fail(LRA_EINVAL, "yin: negative size");
-    yin::Args a{};
-    const int geometry = yin::prepare(a, n, frame_length, hop_length, center, pad_mode, min_period, max_period, trough_threshold, sr, mode);
-    if (geometry == mixed::kGeometryTooShort)
-        return fail(LRA_EINVAL, "yin: input is too short (n=" + std::to_string(n + 2 * (int64_t)a.pad) + ") for frame_length=" + std::to_string(frame_length));
-    if (batch == 0) return LRA_OK;
-    if (!y || (mode == LRA_YIN_F0 ? !f0 : (!frames || !shifts))) return fail(LRA_EINVAL, "null data pointer");
-    if (a.n_frames > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames per clip");
-    if (geometry == mixed::kGeometryLds) return fail(LRA_EINVAL, "yin: max_period=" + std::to_string(max_period) + " does not fit the LDS of a workgroup");
-    a.y = y;
-    a.y_f64 = dtype == LRA_F64;
-    if (a.N > 0) {
-        auto& tw = ctx->cqt_tw[std::make_pair(a.N, (int)LRA_F64)];
-        if (!tw.first) LRA_TRY(mixed_tables(a.N, LRA_F64, &tw.first, &tw.second));
-        a.tw_m = (const mixed::cpx<double>*)tw.first;
-        a.tw_n = (const mixed::cpx<double>*)tw.second;
-    }
-    a.f0 = (double*)f0;
-    a.frames = frames;
-    a.shifts = shifts;
-    if (batch * a.groups > 0x7fffffffLL) return fail(LRA_EINVAL, "yin: too many frames for one launch");
-    LRA_HIP(yin::launch_yin(a, batch, ctx->stream));
-    return LRA_OK;
-}
-
-// ---- the back half of pyin around the decode (lra_pyin.h, launched from lra_pyin_inst.hip) ----------------------------------------------
-static_assert(pyin::kLdsMax == LRA_PYIN_LDS_MAX, "pyin limits");
-static_assert(pyin::geometry(601, 100).waves == 4 && pyin::geometry(4096, 100).lds <= pyin::kLdsMax, "pyin: the default call and the largest state count fit");
-
-int64_t lra_pyin_lds_bytes(int n_pitch_bins, int n_thresholds) {
-    if (n_pitch_bins < 1 || n_thresholds < 1) return 0;
-    const pyin::Geometry g = pyin::geometry(n_pitch_bins, n_thresholds);
-    return g.waves > 1 ? (int64_t)g.lds : (int64_t)pyin::wave_lds(n_pitch_bins, n_thresholds);
-}
-
-int lra_pyin_obs_exec(lra_ctx* ctx, const void* cmnd, const void* shifts, int64_t clips, int n_lags, int64_t n_frames, const void* thresholds, const void* beta_probs,
-                      const void* beta_prefix, const void* boltz_e, const void* boltz_fact, int n_thresholds, double sr, double fmin, int min_period, int n_pitch_bins,
-                      int n_bins_per_semitone, double no_trough_prob, double tiny, double log_tiny, void* log_prob, void* voiced_prob) {
-    LRA_BIND(ctx);
-    if (clips < 0 || n_frames < 0 || n_lags < 2) return fail(LRA_EINVAL, "pyin: need at least 2 lags and non-negative sizes");
-    if (n_thresholds < 1 || n_pitch_bins < 1 || n_bins_per_semitone < 1 || min_period < 1) return fail(LRA_EINVAL, "pyin: n_thresholds, n_pitch_bins, n_bins_per_semitone and min_period must be positive");
-    if (12LL * n_bins_per_semitone > 0x7fffffffLL) return fail(LRA_EINVAL, "pyin: n_bins_per_semitone is too large");
-    if (!(sr > 0) || !(fmin > 0)) return fail(LRA_EINVAL, "pyin: sr and fmin must be positive");
-    if (pyin::wave_lds(n_pitch_bins, n_thresholds) > pyin::kLdsMax)
-        return fail(LRA_EINVAL, "pyin: n_pitch_bins=" + std::to_string(n_pitch_bins) + " with n_thresholds=" + std::to_string(n_thresholds) + " does not fit the LDS of a workgroup");
-    if (clips == 0 || n_frames == 0) return LRA_OK;
-    if (!cmnd || !shifts || !thresholds || !beta_probs || !beta_prefix || !boltz_e || !boltz_fact || !log_prob || !voiced_prob) return fail(LRA_EINVAL, "null data pointer");
-    pyin::ObsArgs a{};
-    a.cmnd = (const double*)cmnd;
-    a.shifts = (const double*)shifts;
-    a.clips = clips;
-    a.n_lags = n_lags;
-    a.T = n_frames;
-    a.thresholds = (const double*)thresholds;
-    a.beta = (const double*)beta_probs;
-    a.beta_prefix = (const double*)beta_prefix;
-    a.boltz_e = (const double*)boltz_e;
-    a.boltz_fact = (const double*)boltz_fact;
-    a.n_thresholds = n_thresholds;
-    a.sr = sr;
-    a.fmin = fmin;
-    a.min_period = min_period;
-    a.P = n_pitch_bins;
-    a.bins_per_octave = 12 * n_bins_per_semitone;
-    a.no_trough_prob = no_trough_prob;
-    a.tiny = tiny;
-    a.log_tiny = log_tiny;
-    a.log_prob = (double*)log_prob;
-    a.voiced_prob = (double*)voiced_prob;
-    a.g = pyin::geometry(n_pitch_bins, n_thresholds);
-    LRA_HIP(pyin::launch_obs(a, ctx->stream));
-    return LRA_OK;
-}
-
-int lra_pyin_finish_exec(lra_ctx* ctx, const void* states, int64_t n, int n_pitch_bins, const void* freqs, int fill, double fill_na, void* f0, void* voiced_flag) {
-    LRA_BIND(ctx);
-    if (n < 0 || n_pitch_bins < 1) return fail(LRA_EINVAL, "pyin: negative size");
-    if (n == 0) return LRA_OK;
-    if (!states || !freqs || !f0 || !voiced_flag) return fail(LRA_EINVAL, "null data pointer");
-    pyin::FinishArgs a{};
-    a.states = (const uint16_t*)states;
-    a.n = n;
-    a.P = n_pitch_bins;
-    a.freqs = (const double*)freqs;
-    a.fill = fill != 0;
-    a.fill_na = fill_na;
-    a.f0 = (double*)f0;
-    a.voiced = (uint8_t*)voiced_flag;
-    LRA_HIP(pyin::launch_finish(a, ctx->stream));
-    return LRA_OK;
-}
-
 int lra_fir_decimate_exec(lra_ctx* ctx, const void* x, void* out, int64_t batch, int64_t n_in, int64_t n_out, const void* taps, int n_taps, int down, int first, double div, double mul,
                           int dtype) {
     LRA_BIND(ctx);
@@ -4126,13 +3074,13 @@ int lra_cqt_octave_exec(lra_ctx* ctx, const void* y, int64_t batch, int64_t n, i
     if (!y || !out || !row_ptr || !col || !val) return fail(LRA_EINVAL, "null data pointer");
     if (n_frames > 1 + n / hop) return fail(LRA_EINVAL, "cqt_octave: more frames than the centred signal has");
     if (n_frames > 0x7fffffffLL / 4) return fail(LRA_EINVAL, "too many frames per clip");
-    auto& tw = ctx->cqt_tw[std::make_pair(n_fft, dtype)];
-    if (!tw.first) LRA_TRY(mixed_tables(n_fft, dtype, &tw.first, &tw.second));
+    const void *tw_m = nullptr, *tw_n = nullptr;
+    LRA_TRY(ctx_twiddles(ctx, n_fft, dtype, &tw_m, &tw_n));
     const int F = mixed::cqt_frames_per_group_of(n_fft, dtype == LRA_F64 ? 8 : 4);
     auto fill = [&](auto& a, auto tag) {
         using T = decltype(tag);
         a.y = (const T*)y; a.y_stride = y_stride; a.n = n; a.hop = hop; a.pad = n_fft / 2; a.pad_mode = pad_mode;
-        a.tw_m = (const mixed::cpx<T>*)tw.first; a.tw_n = (const mixed::cpx<T>*)tw.second;
+        a.tw_m = (const mixed::cpx<T>*)tw_m; a.tw_n = (const mixed::cpx<T>*)tw_n;
         a.row_ptr = (const int*)row_ptr; a.col = (const int*)col; a.val = (const mixed::cpx<T>*)val; a.sqrt_len = (const double*)sqrt_len;
         a.out = (mixed::cpx<T>*)out; a.n_frames = (int)n_frames; a.n_total = n_total; a.bin0 = bin0; a.row0 = row0; a.n_rows = n_rows;
         a.groups_per_clip = (int)((n_frames + F - 1) / F);
@@ -4160,8 +3108,8 @@ template <class T>
 int cqt_octaves_merged(lra_ctx* ctx, const lra_cqt_octave* octaves, const char* const* ys, int i0, int i1, int64_t batch, int pad_mode, const double* sqrt_len, void* out, int64_t n_frames,
                        int n_total, int dtype) {
     const int n_fft = octaves[i0].n_fft;
-    auto& tw = ctx->cqt_tw[std::make_pair(n_fft, dtype)];
-    if (!tw.first) LRA_TRY(mixed_tables(n_fft, dtype, &tw.first, &tw.second));
+    const void *tw_m = nullptr, *tw_n = nullptr;
+    LRA_TRY(ctx_twiddles(ctx, n_fft, dtype, &tw_m, &tw_n));
     const int F = mixed::cqt_frames_per_group_of(n_fft, (int)sizeof(T));
     mixed::CqtMultiArgs<T> m = mixed::CqtMultiArgs<T>();
     m.n_oct = 0;
@@ -4176,7 +3124,7 @@ int cqt_octaves_merged(lra_ctx* ctx, const lra_cqt_octave* octaves, const char* 
         if (n_frames > 1 + o.n / o.hop) return fail(LRA_EINVAL, "cqt_octave: more frames than the centred signal has");
         mixed::CqtArgs<T>& a = m.oct[m.n_oct++];
         a.y = (const T*)ys[i]; a.y_stride = o.n; a.n = o.n; a.hop = o.hop; a.pad = n_fft / 2; a.pad_mode = pad_mode;
-        a.tw_m = (const mixed::cpx<T>*)tw.first; a.tw_n = (const mixed::cpx<T>*)tw.second;
+        a.tw_m = (const mixed::cpx<T>*)tw_m; a.tw_n = (const mixed::cpx<T>*)tw_n;
         a.row_ptr = (const int*)o.row_ptr; a.col = (const int*)o.col; a.val = (const mixed::cpx<T>*)o.val; a.sqrt_len = sqrt_len ? sqrt_len + o.bin0 : nullptr;
         a.out = (mixed::cpx<T>*)out; a.n_frames = (int)n_frames; a.n_total = n_total; a.bin0 = o.bin0; a.row0 = o.row0; a.n_rows = o.n_rows;
         a.groups_per_clip = groups;

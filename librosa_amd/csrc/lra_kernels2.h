@@ -22,7 +22,8 @@
 //     butterflies are self-mirrored); a handful of lane-0 selects and a second pair of store bases absorb that.
 //
 // Applies to configurations whose last pass has two butterflies per thread (R / r_last == 2): n_fft 1024, 2048, 4096
-// at 16 points per thread.  Everything else keeps stft_block.
+// and 16384 at 16 points per thread in float32 (v2_cfg_ok below; n_fft = 8192 ends on a full-width pass and does not qualify).  Everything else
+// keeps stft_block.
 #pragma once
 
 #include "lra_kernels.h"

@@ -1,4 +1,4 @@
-// lra_mixed_launch.h -- what lra_api.hip sees of the mixed-radix kernels: the frame lengths they are instantiated for (lra_mixed_sizes.h,
+// lra_mixed_launch.h -- what lra_api.hip (and the tempogram and YIN units, for the table sizes) sees of the mixed-radix kernels: the frame lengths they are instantiated for (lra_mixed_sizes.h,
 // checked here against what the kernels can factor) and the launchers (defined in lra_mixed_inst.hip).
 #pragma once
 

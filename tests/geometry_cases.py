@@ -5,22 +5,23 @@ computed them: for every ``stft_iters``, ``istft_strip_groups`` and ``xcd_remap`
 (tests/test_launch_geometry_gpu.py on the device, tests/test_launch_geometry_host.py through the host simulator).
 
 One entry per kernel family.  ``sel`` cites the lines of librosa_amd/csrc/lra_api.hip that select the family's kernel, ``fpb`` is the number
-of frame slots (forward) or strips (inverse) of one workgroup with the line it was read from in ``fpb_from``.
+of frame slots (forward) or strips (inverse) of one workgroup with the line it was read from in ``fpb_from``.  Lines of lra_api.hip are cited by
+named anchor, ``file [tag] [tag]``: the tag stands in a comment on the cited line (tests/test_launch_geometry_host.py checks that each exists).
 
 FPB = NT / TF (lra_fft.h:44-46) with TF = M / R threads per frame, R = 16 (float32: lra_dispatch.h:25-27) or 8 (float64: lra_dispatch.h:28-30) and
 NT = max(TF, 64); the mel kernels run the same transform with NT = 256 (lra_dispatch.h:112-115), the many-band form with NT = 128
-(lra_dispatch.h:119-122); the producer / consumer kernel has NP = 2 producer slots (lra_api.hip:503, PcLayout::NP)."""
+(lra_dispatch.h:119-122); the producer / consumer kernel has NP = 2 producer slots (lra_api.hip [geo:pc-np], PcLayout::NP)."""
 from collections import namedtuple
 
 # ---- geometry values the issue asks for ---------------------------------------------------------------------------------------------
 STFT_ITERS = (1, 2, 3, 4, 5, 7, 8, 9, 13, 24)  # + one value above the clip's frame count (forward_points)
 ISTFT_STRIPS = (1, 2, 3, 5, 8, 32, 176)        # + one value above n_used (inverse_points)
 MAX_FRAMES = 72                                 # clips stay tiny
-EDGE_GRIDS = (63, 64, 65, 71, 72)               # 63: last unmapped grid, 64: first mapped one, 65 / 71: padded by 7 / by 1 (lra_api.hip:485, 530, 723)
+EDGE_GRIDS = (63, 64, 65, 71, 72)               # 63: last unmapped grid, 64: first mapped one, 65 / 71: padded by 7 / by 1 (lra_api.hip [geo:xcd-pad] [geo:pc-xcd-pad] [geo:istft-xcd-pad])
 HOST_ITERS = (1, 3, 5, 8)
 HOST_STRIPS = (1, 3, 8)
 
-# what every test puts back in its `finally` block (the library's defaults, lra_api.hip:82-121)
+# what every test puts back in its `finally` block (the library's defaults, lra_internal.h [ctx:defaults])
 OPTION_DEFAULTS = dict(stft_iters=0, istft_strip_groups=0, xcd_remap=1, mel_pc=1, mel_runs=1, generic_mel=0, variant=-1, direct=1, istft16=0)
 
 Forward = namedtuple("Forward", "name kind n_fft hop dtype power n_mels opts fpb fpb_from sel sim bar")
@@ -43,61 +44,61 @@ def _both(name, n_fft, hop, **kw):
 
 FORWARD = []
 # general ring (RA = 0), float32: a hop that is no whole number of ring rows and no divisor of n_fft
-# lra_api.hip:386-388 (the default instance; none of 390, 398, 407, 420 applies)
-FORWARD += _both("ring-general-f32", 512, 100, fpb=4, fpb_from=_F32, sel="lra_api.hip:386-388", sim=dict(ring_aligned=0, v2=0))
-# ... float64: ring_rows_aligned is consulted for float32 only (lra_api.hip:389)
-FORWARD += _both("ring-general-f64", 512, 128, dtype="float64", fpb=2, fpb_from=_F64, sel="lra_api.hip:386-389", sim=dict(ring_aligned=0, v2=0))
-# row-aligned ring (RA = 1) with four slots per wave: the rot_uniform path (lra_api.hip:465-469).  At n_fft = 512 the register ring
-# (lra_api.hip:406-412) takes hop n_fft / 4 by default, so the family is reached with the context option direct = 0 (lra_api.hip:407)
+# lra_api.hip [sel:ring] (the default instance; none of [sel:ringrows] [sel:direct] [sel:regring] [sel:v2] applies)
+FORWARD += _both("ring-general-f32", 512, 100, fpb=4, fpb_from=_F32, sel="lra_api.hip [sel:ring]", sim=dict(ring_aligned=0, v2=0))
+# ... float64: ring_rows_aligned is consulted for float32 only (lra_api.hip [sel:ringrows-f32])
+FORWARD += _both("ring-general-f64", 512, 128, dtype="float64", fpb=2, fpb_from=_F64, sel="lra_api.hip [sel:ring] [sel:ringrows-f32]", sim=dict(ring_aligned=0, v2=0))
+# row-aligned ring (RA = 1) with four slots per wave: the rot_uniform path (lra_api.hip [geo:rot-uniform]).  At n_fft = 512 the register ring
+# (lra_api.hip [sel:regring]) takes hop n_fft / 4 by default, so the family is reached with the context option direct = 0 (same line)
 # -- and, with every option at its default, by the mel families "mel-many", "mel-masked" and "mel-generic" below (hop n_fft / 4).
-FORWARD += _both("ring-rows-n512", 512, 128, opts=dict(direct=0), fpb=4, fpb_from=_F32, sel="lra_api.hip:389-394 (407: direct = 0)")
+FORWARD += _both("ring-rows-n512", 512, 128, opts=dict(direct=0), fpb=4, fpb_from=_F32, sel="lra_api.hip [sel:ringrows-f32] [sel:ringrows] ([sel:regring]: direct = 0)")
 # direct framing (RA = 2): hop >= n_fft
-FORWARD += _both("direct-n512", 512, 640, fpb=4, fpb_from=_F32, sel="lra_api.hip:397-403", sim=dict(v2=0))
+FORWARD += _both("direct-n512", 512, 640, fpb=4, fpb_from=_F32, sel="lra_api.hip [sel:direct]", sim=dict(v2=0))
 # register ring (RA = 3 .. 6): n_fft = 8192 with hop n_fft / 2, / 4, / 8, / 16; and the four-slot form at n_fft = 512
 for _hd in (2, 4, 8, 16):
-    FORWARD += _both(f"regring-n8192-hd{_hd}", 8192, 8192 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip:406-412", sim=dict(v2=0) if _hd == 4 else None)
-FORWARD += _both("regring-n512-hd4", 512, 128, fpb=4, fpb_from=_F32, sel="lra_api.hip:406-412", sim=dict(v2=0))
+    FORWARD += _both(f"regring-n8192-hd{_hd}", 8192, 8192 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip [sel:regring]", sim=dict(v2=0) if _hd == 4 else None)
+FORWARD += _both("regring-n512-hd4", 512, 128, fpb=4, fpb_from=_F32, sel="lra_api.hip [sel:regring]", sim=dict(v2=0))
 # stft2_kernel, HD = 1, 2, 4, 8 at n_fft = 1024 (two slots per wave) and 4096 (two waves per frame)
 for _hd in (1, 2, 4, 8):
-    FORWARD += _both(f"stft2-n1024-hd{_hd}", 1024, 1024 // _hd, fpb=2, fpb_from=_F32, sel="lra_api.hip:419-430", sim=dict(v2=1))
-    FORWARD += _both(f"stft2-n4096-hd{_hd}", 4096, 4096 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip:419-430", sim=dict(v2=1) if _hd == 4 else None)
+    FORWARD += _both(f"stft2-n1024-hd{_hd}", 1024, 1024 // _hd, fpb=2, fpb_from=_F32, sel="lra_api.hip [sel:v2]", sim=dict(v2=1))
+    FORWARD += _both(f"stft2-n4096-hd{_hd}", 4096, 4096 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip [sel:v2]", sim=dict(v2=1) if _hd == 4 else None)
 # n_fft = 2048: the complex epilogue runs in the radix 16-16-4 form (variant 6), |X|^2 in stft2_kernel on the 16-8-8 core
-FORWARD += [_fwd(f"radix-16-16-4-hd{_hd}-complex", "stft", 2048, 2048 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip:1194, 1206 (variant 6), 540-542, 419-430")
+FORWARD += [_fwd(f"radix-16-16-4-hd{_hd}-complex", "stft", 2048, 2048 // _hd, fpb=1, fpb_from=_F32, sel="lra_api.hip [sel:v2-applies] [sel:variant-fwd] (variant 6) [sel:plan1] [sel:v2]")
             for _hd in (4, 8)]
-FORWARD += [_fwd("stft2-n2048-hd4-power", "power", 2048, 512, fpb=1, fpb_from=_F32, sel="lra_api.hip:1206-1207 (variant 0), 419-430", sim=dict(v2=1))]
+FORWARD += [_fwd("stft2-n2048-hd4-power", "power", 2048, 512, fpb=1, fpb_from=_F32, sel="lra_api.hip [sel:variant-fwd] (variant 0) [sel:v2]", sim=dict(v2=1))]
 
 # ---- fused mel --------------------------------------------------------------------------------------------------------------------
-_PC = "lra_api.hip:503 (PcLayout::NP = 2)"
+_PC = "lra_api.hip [geo:pc-np] (PcLayout::NP = 2)"
 FORWARD += [
     # stft_pc_kernel: HD = 4 serves |X|^2, HD = 8 serves |X| and |X|^2 (pc_fits_budget); 128 and 125 bands
-    _fwd(f"mel-pc-hd{4 if hop == 512 else 8}-p{int(p)}-{nm}", "mel", 2048, hop, power=p, n_mels=nm, fpb=2, fpb_from=_PC, sel="lra_api.hip:566-577, 493-534", bar="mel-rel")
+    _fwd(f"mel-pc-hd{4 if hop == 512 else 8}-p{int(p)}-{nm}", "mel", 2048, hop, power=p, n_mels=nm, fpb=2, fpb_from=_PC, sel="lra_api.hip [sel:mel-pc] [sel:launch-pc]", bar="mel-rel")
     for hop, p in ((512, 2.0), (256, 1.0), (256, 2.0)) for nm in (128, 125)
 ]
 FORWARD += [
     # the one-wave run-ordered kernel, stft2_kernel<OUT_MELR> in 256-thread workgroups
-    _fwd("mel-onewave", "mel", 2048, 512, n_mels=128, opts=dict(mel_pc=0), fpb=4, fpb_from=_MEL, sel="lra_api.hip:580-595 (568: mel_pc = 0)", bar="mel-rel"),
+    _fwd("mel-onewave", "mel", 2048, 512, n_mels=128, opts=dict(mel_pc=0), fpb=4, fpb_from=_MEL, sel="lra_api.hip [sel:mel-onewave] ([sel:mel-pc]: mel_pc = 0)", bar="mel-rel"),
     # the many-band small-frame form: n_fft = 512 with more than 100 bands, eight slots of sixteen threads
-    _fwd("mel-many", "mel", 512, 128, n_mels=128, fpb=8, fpb_from="lra_fft.h:44-46 with lra_dispatch.h:119-122 (NT = 128)", sel="lra_api.hip:597-613, 2485"),
-    # the masked two-slope fallback; staging tile 4 (lra_api.hip:633), so stft_iters 1 .. 3 exercise the clamp mel_tile = iters (lra_api.hip:470-471)
-    _fwd("mel-masked", "mel", 2048, 512, n_mels=128, opts=dict(mel_runs=0), fpb=4, fpb_from=_MEL, sel="lra_api.hip:631-644 (568, 581, 614: mel_runs = 0)"),
-    # the generic banded path; staging tile 4 (lra_api.hip:470)
-    _fwd("mel-generic", "mel", 2048, 512, n_mels=128, opts=dict(generic_mel=1), fpb=1, fpb_from=_F32, sel="lra_api.hip:1167 (generic_mel = 1), 650"),
+    _fwd("mel-many", "mel", 512, 128, n_mels=128, fpb=8, fpb_from="lra_fft.h:44-46 with lra_dispatch.h:119-122 (NT = 128)", sel="lra_api.hip [sel:mel-many] [sel:mel-many-plan]"),
+    # the masked two-slope fallback; staging tile 4 (lra_api.hip [geo:staging-tile]), so stft_iters 1 .. 3 exercise the clamp mel_tile = iters (lra_api.hip [geo:mel-tile])
+    _fwd("mel-masked", "mel", 2048, 512, n_mels=128, opts=dict(mel_runs=0), fpb=4, fpb_from=_MEL, sel="lra_api.hip [sel:mel-masked] ([sel:mel-pc] [sel:mel-onewave] [sel:mel-runs]: mel_runs = 0)"),
+    # the generic banded path; staging tile 4 (lra_api.hip [geo:mel-tile])
+    _fwd("mel-generic", "mel", 2048, 512, n_mels=128, opts=dict(generic_mel=1), fpb=1, fpb_from=_F32, sel="lra_api.hip [sel:generic-mel-option] (generic_mel = 1) [sel:mel-generic]"),
 ]
-STAGING_TILE = 4  # lra_api.hip:470, 633: the two staged mel families run with stft_iters below it
+STAGING_TILE = 4  # lra_api.hip [geo:mel-tile] [geo:staging-tile]: the two staged mel families run with stft_iters below it
 
 # ---- inverse ----------------------------------------------------------------------------------------------------------------------
 INVERSE = [
-    # istft_kernel<Cfg, 0>: a hop that is no whole number of rows (n_fft = 2048: lra_api.hip:1358 sends 256 / 512 / 1024 to another kernel), and float64
-    Inverse("general-f32", 2048, 300, "float32", {}, 1, _F32, "lra_api.hip:682 (none of 684-694), 1391 (variant 0)", None),
-    Inverse("general-f64", 512, 128, "float64", {}, 2, _F64, "lra_api.hip:682-683 (row forms are float32 only)", dict(ring_aligned=0)),
+    # istft_kernel<Cfg, 0>: a hop that is no whole number of rows (n_fft = 2048: lra_api.hip [sel:istft-mixed-pow2] sends 256 / 512 / 1024 to another kernel), and float64
+    Inverse("general-f32", 2048, 300, "float32", {}, 1, _F32, "lra_api.hip [sel:istft-general] (no form of [sel:istft-rows]) [sel:variant-inv] (variant 0)", None),
+    Inverse("general-f64", 512, 128, "float64", {}, 2, _F64, "lra_api.hip [sel:istft-general] [sel:istft-rows] (row forms are float32 only)", dict(ring_aligned=0)),
 ]
 # the row-aligned forms HC = R / 2, R / 4, R / 8, R / 16 with four strips per workgroup
-INVERSE += [Inverse(f"rows-n512-hc-r{d}", 512, 512 // d, "float32", {}, 4, _F32, "lra_api.hip:683-695", dict(ring_aligned=1)) for d in (2, 4, 8, 16)]
+INVERSE += [Inverse(f"rows-n512-hc-r{d}", 512, 512 // d, "float32", {}, 4, _F32, "lra_api.hip [sel:istft-rows]", dict(ring_aligned=1)) for d in (2, 4, 8, 16)]
 INVERSE += [
     # n_fft = 2048, hop n_fft / 4: radices 8, 8, 16 by default (variant 5), radices 4, 16, 16 with istft16 = 1 (variant 7)
-    Inverse("n2048-8-8-16", 2048, 512, "float32", {}, 1, _F32, "lra_api.hip:1396-1397 (variant 5), 667-669, 683-695", None),
-    Inverse("n2048-4-16-16", 2048, 512, "float32", dict(istft16=1), 1, _F32, "lra_api.hip:1396-1397 (variant 7), 667-669, 683-695", None),
-    Inverse("n2048-4-16-16-hd8", 2048, 256, "float32", dict(istft16=1), 1, _F32, "lra_api.hip:1396-1397 (variant 7), 667-669, 683-695", None),
+    Inverse("n2048-8-8-16", 2048, 512, "float32", {}, 1, _F32, "lra_api.hip [sel:variant-inv] (variant 5) [sel:istft-plan1] [sel:istft-rows]", None),
+    Inverse("n2048-4-16-16", 2048, 512, "float32", dict(istft16=1), 1, _F32, "lra_api.hip [sel:variant-inv] (variant 7) [sel:istft-plan1] [sel:istft-rows]", None),
+    Inverse("n2048-4-16-16-hd8", 2048, 256, "float32", dict(istft16=1), 1, _F32, "lra_api.hip [sel:variant-inv] (variant 7) [sel:istft-plan1] [sel:istft-rows]", None),
 ]
 
 FORWARD_BY_NAME = {f.name: f for f in FORWARD}
@@ -170,17 +171,17 @@ EDGE_STRIPS = 3   # inverse: clips of EDGE_STRIPS frames and istft_strip_groups 
 
 
 def forward_grid(batch, n_frames, iters, fpb):
-    """StftLaunch::launch / launch_pc: lra_api.hip:472-476, 523-527."""
+    """StftLaunch::launch / launch_pc: lra_api.hip [geo:strips] [geo:pc-strips]."""
     return batch * -(-n_frames // (fpb * iters))
 
 
 def inverse_grid(batch, n_used, strips, fpb):
-    """IstftLaunch::run: lra_api.hip:715-716."""
+    """IstftLaunch::run: lra_api.hip [geo:istft-strips]."""
     return -(-(batch * -(-n_used // strips)) // fpb)
 
 
 def launched(grid, xcd_remap=1):
-    """Workgroups launched for `grid` work items: padded to a multiple of 8 from 64 on (lra_api.hip:485-486)."""
+    """Workgroups launched for `grid` work items: padded to a multiple of 8 from 64 on (lra_api.hip [geo:xcd-pad])."""
     return -(-grid // 8) * 8 if (xcd_remap and grid >= 64) else grid
 
 

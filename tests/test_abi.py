@@ -1,4 +1,5 @@
-"""The C-ABI library loads and exports every symbol include/librosa_amd.h declares (CPU: no compute calls)."""
+"""The C-ABI library loads and exports every symbol include/librosa_amd.h declares, with one error slot for all of its translation units
+(CPU: no compute calls)."""
 import ctypes
 import os
 import re
@@ -71,3 +72,24 @@ def test_product_never_imports_the_oracle():
                 code = "\n".join(line for line in txt.splitlines() if not line.lstrip().startswith(("//", "#  ", "*", '"""')))
                 m = bad.search(code)
                 assert m is None, (os.path.join(dirpath, f), m.group(0))
+
+
+# one entry point of each family whose C entry points are defined beside their kernels (csrc/lra_<feature>_inst.hip), not in lra_api.hip
+_FEATURE_UNIT_ENTRY_POINTS = ("lra_tempogram_exec", "lra_beat_exec", "lra_peak_pick_exec", "lra_prev_minimum_exec", "lra_chroma_exec", "lra_piptrack_exec", "lra_tuning_exec",
+                              "lra_viterbi_exec", "lra_dtw_cost_exec", "lra_rqa_score_exec", "lra_knn_select_exec", "lra_yin_exec", "lra_pyin_obs_exec")
+
+
+@pytest.mark.parametrize("name", _FEATURE_UNIT_ENTRY_POINTS)
+def test_one_error_slot_across_translation_units(name):
+    """A failure raised in a feature unit is what lra_last_error() (defined in lra_api.hip) reports, and a later failure in the API unit
+    replaces it: the library has one thread-local error slot, not one per translation unit.  No device needed: a null context fails first."""
+    from librosa_amd import _native
+
+    lib = _native.load_library()
+    _, argtypes = _native.SIGNATURES[name]
+    assert lib.lra_device_count(None) == _native.LRA_EINVAL and lib.lra_last_error() == b"null count"  # the slot holds an API-unit message
+    assert getattr(lib, name)(*(t() for t in argtypes)) == _native.LRA_EINVAL  # every argument zero / null
+    assert lib.lra_last_error() == b"null context"
+    assert lib.lra_device_count(None) == _native.LRA_EINVAL and lib.lra_last_error() == b"null count"
+    assert lib.lra_stft_plan_create(*(t() for t in _native.SIGNATURES["lra_stft_plan_create"][1])) == _native.LRA_EINVAL
+    assert lib.lra_last_error() == b"null context"

@@ -663,6 +663,37 @@ def test_large_frame_ring_forms(L, hop):
             assert np.abs(S - Sr).max() <= 8e-6 * np.abs(Sr).max(), (hop, n, center, pad_mode, power)
 
 
+@pytest.mark.parametrize("clips", [1, 2])
+@pytest.mark.parametrize("hd", [1, 2, 4, 8])
+def test_second_generation_kernel_n16384(L, hd, clips):
+    """n_fft = 16384 with hop = n_fft / {1, 2, 4, 8}: the second-generation forward kernel (csrc/lra_fused.h, instance group 13) -- complex, magnitude,
+    power and general-power epilogues on 3 n_fft + 1 samples, against the oracle with the bars of test_large_frame_ring_forms."""
+    n_fft, hop = 16384, 16384 // hd
+    y = np.random.default_rng(n_fft + hd + clips).standard_normal((clips, 3 * n_fft + 1)).astype(np.float32)
+    kw = dict(n_fft=n_fft, hop_length=hop)
+    D, ref = L.stft(y, **kw), O.stft(y, **kw)
+    assert D.shape == ref.shape and _stft_close(D, ref)
+    for power in (1.0, 2.0, 1.5):
+        S, _ = L.core.spectrum._spectrogram(y=y, power=power, **kw)
+        Sr, _ = O.spectrogram(y=y, power=power, **kw)
+        assert np.abs(S - Sr).max() <= 8e-6 * np.abs(Sr).max(), power
+
+
+@pytest.mark.parametrize("clips", [1, 2])
+@pytest.mark.parametrize("hd", [1, 2, 4, 8])
+@pytest.mark.parametrize("n_fft", [1024, 4096, 16384])
+def test_second_generation_mel_epilogue_beside_n2048(L, n_fft, hd, clips):
+    """Fused mel with 128 bands at n_fft 1024 / 4096 / 16384 and hop = n_fft / {1, 2, 4, 8}: the run-ordered epilogue of the second-generation kernel in
+    256-thread (mel) workgroups (csrc/lra_fused.h, instance group 14; n_fft = 2048 has the tests above) -- |X|, |X|^2 and |X|^1.5 on 3 n_fft + 1
+    samples, against the oracle at the mel bar."""
+    hop = n_fft // hd
+    y = np.random.default_rng(n_fft + hd + clips).standard_normal((clips, 3 * n_fft + 1)).astype(np.float32)
+    for power in (1.0, 2.0, 1.5):
+        kw = dict(y=y, sr=22050, n_fft=n_fft, hop_length=hop, n_mels=128, power=power)
+        M, ref = L.feature.melspectrogram(**kw), O.melspectrogram(**kw)
+        assert M.shape == ref.shape and not np.isnan(M).any() and _mel_close(M, ref), power
+
+
 # ---------------------------------------------------------------------------------------------------
 # 5. decibel scaling and MFCC (SURVEY.md 8f ranks 1, 2)
 # ---------------------------------------------------------------------------------------------------
@@ -1510,6 +1541,25 @@ def test_istft_sixteenth_hop(L, n_fft, hop):
         wss = _wss_for(dict(n_fft=n_fft, hop_length=hop), D.shape[-1], ref.shape[-1], length, np.float32)
         assert got.shape == ref.shape and _istft_close(got, ref, wss)
     assert np.abs(L.istft(D, hop_length=hop, length=y.shape[-1]) - y).max() <= 2e-5
+
+
+@pytest.mark.parametrize("clips", [1, 2])
+def test_istft_ascending_radix_general_hop(L, clips):
+    """Context option variant = 5 pins the inverse to the ascending-radix configuration (radices 8, 8, 16); with a hop that is no whole number of
+    rows it runs the general overlap-add mode there (istft_kernel<cfg_f32_10r, 0>, csrc/lra_fused.h instance group 13), which no default call
+    reaches.  3 n_fft + 1 samples against the oracle with the inverse's bar."""
+    n_fft, hop = 2048, 300
+    ctx = L.get_context(0)
+    y = np.random.default_rng(n_fft + hop + clips).standard_normal((clips, 3 * n_fft + 1)).astype(np.float32)
+    D = O.stft(y, n_fft=n_fft, hop_length=hop)
+    ref = O.istft(D, hop_length=hop)
+    wss = _wss_for(dict(n_fft=n_fft, hop_length=hop), D.shape[-1], ref.shape[-1], None, np.float32)
+    try:
+        ctx.set_option("variant", 5)
+        got = L.istft(D, hop_length=hop)
+    finally:
+        ctx.set_option("variant", -1)
+    assert got.shape == ref.shape and _istft_close(got, ref, wss)
 
 
 @pytest.mark.parametrize(

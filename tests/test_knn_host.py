@@ -243,7 +243,7 @@ def test_exported_names():
     assert "knn_inst" in build.UNITS
     header = open(os.path.join(ROOT, "include", "librosa_amd.h")).read()
     assert f"#define LRA_KNN_MAX_K {_native.Context.KNN_MAX_K}" in header and f"#define LRA_KNN_WORK_BYTES {_native.Context.KNN_WORK_BYTES}" in header
-    api = open(os.path.join(ROOT, "librosa_amd", "csrc", "lra_api.hip")).read()
+    api = open(os.path.join(ROOT, "librosa_amd", "csrc", "lra_knn_inst.hip")).read()  # the unit that defines the entry points, beside their kernels
     for name in ("lra_knn_lds_bytes", "lra_knn_select_exec", "lra_knn_mutual_exec", "lra_knn_bandwidth_exec", "lra_knn_bw_check_exec", "lra_knn_emit_exec", "lra_knn_dense_exec"):
         assert name in _native.SIGNATURES and name in header and name in api
     for word, code in list(_native.Context.KNN_MODES.items()) + [("bw_" + k, v) for k, v in _native.Context.KNN_BW_MODES.items() if v]:

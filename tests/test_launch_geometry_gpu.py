@@ -185,7 +185,7 @@ def test_forward_more_than_one_round(L, name):
     n_cu = _n_cu()
     batch = G.rounds_batch(n_cu, fam.fpb)
     assert G.forward_grid(batch, G.ROUNDS_FRAMES, 1, fam.fpb) >= 3 * n_cu * G.WAVE_SLOTS_PER_CU
-    assert batch * G.ROUNDS_FRAMES < 65536, "below the size at which the library times its tuning variants (lra_api.hip:1197)"
+    assert batch * G.ROUNDS_FRAMES < 65536, "below the size at which the library times its tuning variants (lra_api.hip [sel:autotune])"
     y = _forward_input(fam, batch, G.ROUNDS_FRAMES)
     yt = torch.from_numpy(y).to("cuda:0")
     with _options(ctx, **fam.opts):

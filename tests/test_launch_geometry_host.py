@@ -7,6 +7,10 @@ this file says whether the kernel's logic is wrong or only its compiled form: a 
 No family differs between two geometries in the simulator.  The inverse's overlap-add has no geometry-dependent order of additions either: a strip
 starts from a zero carry and replays the ceil(n_fft / hop) - 1 frames before its own (lra_kernels.h: istft_block, `t = s.t0 - a.warm_frames + j`), so an
 output sample is always 0 + its frames' contributions in ascending frame order."""
+import functools
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -80,7 +84,7 @@ def test_sim_forward_result_does_not_depend_on_iters(name, monkeypatch):
 
 # ---- inverse --------------------------------------------------------------------------------------------------------------------------
 def _sim_inverse_variant(fam):
-    """The configuration lra_api.hip:1391-1397 picks: radices 4, 16, 16 with istft16 = 1, else 8, 8, 16 at n_fft = 2048 with a row-aligned hop."""
+    """The configuration lra_api.hip [sel:variant-inv] picks: radices 4, 16, 16 with istft16 = 1, else 8, 8, 16 at n_fft = 2048 with a row-aligned hop."""
     if fam.opts.get("istft16"):
         return 7
     return 5 if fam.name == "n2048-8-8-16" else 0
@@ -119,12 +123,37 @@ def test_sim_inverse_result_does_not_depend_on_strips(name, use_length):
 
 
 # ---- the case list ----------------------------------------------------------------------------------------------------------------------
+def _cited_tags(text):
+    """[(file, "[tag]")] of every ``file [tag] [tag] (remark) [tag]`` citation in `text`: a tag belongs to the file named last before it."""
+    out, fname = [], None
+    for m in re.finditer(r"(lra_\w+\.(?:hip|h))|(\[[a-z]+:[\w-]+\])", text):
+        if m.group(1):
+            fname = m.group(1)
+        else:
+            assert fname, text
+            out.append((fname, m.group(2)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _csrc(fname):
+    return open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "librosa_amd", "csrc", fname)).read()
+
+
 def test_every_family_has_a_selection_comment_and_an_fpb():
+    # every named anchor the case list cites, in a family's entry or in a comment, stands in the file it is cited from
+    every = _cited_tags(open(G.__file__).read())
+    assert len(every) > 40
+    for fname, tag in every:
+        assert tag in _csrc(fname), (fname, tag)
     names = set()
     for fam in G.FORWARD + G.INVERSE:
         assert fam.name not in names
         names.add(fam.name)
-        assert "lra_api.hip:" in fam.sel and any(c.isdigit() for c in fam.sel), fam.name
+        cited = _cited_tags(fam.sel)
+        assert cited and cited[0][0] == "lra_api.hip", fam.name
+        for fname, tag in cited + _cited_tags(fam.fpb_from):
+            assert tag in _csrc(fname), (fam.name, fname, tag)
         assert isinstance(fam.fpb, int) and fam.fpb >= 1 and ":" in fam.fpb_from, fam.name
         assert fam.n_fft & (fam.n_fft - 1) == 0, "power-of-two kernels only"
         assert set(fam.opts) <= set(G.OPTION_DEFAULTS), fam.name
