@@ -565,6 +565,47 @@ int lra_knn_emit_exec(lra_ctx* ctx, int64_t n, int64_t m, int k, const void* cou
 int lra_knn_dense_exec(lra_ctx* ctx, const void* Q, const void* R, int dtype, int64_t n_features, int64_t n, int64_t m, int metric, int64_t width, int self, int mode, int bw_mode,
                        double bw_scalar, int bw_on_device, const void* sigma, const void* matrix, void* work, void* out);
 
+/* ---- segment.path_enhance, util.shear / recurrence_to_lag / lag_to_recurrence, feature.stack_memory: librosa/segment.py:1167-1329, :709-891,
+ * librosa/util/utils.py:2136-2260, librosa/feature/utils.py:134-314 ------------------------------------------------------------------------- */
+#define LRA_ENHANCE_LDS_MAX (160 * 1024)
+#define LRA_ENHANCE_MAX_REACH 124 /* rows, and columns, the filters of one call may span beyond one cell: that halo fits the LDS next to the smallest tile */
+#define LRA_ENHANCE_REFLECT 0     /* scipy.ndimage's boundary modes */
+#define LRA_ENHANCE_CONSTANT 1
+#define LRA_ENHANCE_NEAREST 2
+#define LRA_ENHANCE_MIRROR 3
+#define LRA_ENHANCE_WRAP 4
+#define LRA_STACK_CONSTANT 0 /* np.pad's modes */
+#define LRA_STACK_EDGE 1
+#define LRA_STACK_REFLECT 2
+#define LRA_STACK_SYMMETRIC 3
+#define LRA_STACK_WRAP 4
+/* One non-zero weight of a filter: out[i][j] += R[ext(i + dr)][ext(j + dc)] * w. */
+typedef struct lra_enhance_tap {
+    int32_t dr, dc;
+    double w;
+} lra_enhance_tap;
+/* Bytes of the device table lra_path_enhance_exec writes for n_taps taps in n_filters filters. */
+#define LRA_ENHANCE_TABLE_BYTES(n_taps, n_filters) ((((size_t)(n_filters) + 1) * 4 + 15) / 16 * 16 + 16 * (size_t)(n_taps))
+/* Bytes of LDS a workgroup of lra_path_enhance_exec needs (host arithmetic only) for an output tile of rows x cols cells under a halo of
+ * halo_rows rows and halo_cols columns; rows == cols == 0: the library's choice.  0 for a geometry that is not served: rows 1 .. 256, cols
+ * 16, 32 or 64, rows * cols <= 4096, and tile plus halo as float64 within LRA_ENHANCE_LDS_MAX. */
+int64_t lra_enhance_lds_bytes(int rows, int cols, int halo_rows, int halo_cols);
+/* np.maximum over the n_filters responses scipy.ndimage.convolve gives, then np.clip(., 0, None) with `clip`: R and out [channels][h][w] of
+ * `dtype` (LRA_F32 or LRA_F64; device, R never written).  taps (host): the non-zero weights of filter f at starts[f] .. starts[f + 1] - 1
+ * (starts: host, n_filters + 1 entries from 0), summed in that order in float64 from 0, every product and sum rounded on its own; a float32
+ * response is rounded once.  ext: `mode` (LRA_ENHANCE_*), LRA_ENHANCE_CONSTANT reads cval outside.  All taps lie within a box of at most
+ * LRA_ENHANCE_MAX_REACH rows and columns around the cell.  table: LRA_ENHANCE_TABLE_BYTES of device scratch (this waits for the stream while it
+ * is filled).  (rows, cols): the tile, 0, 0 for the library's choice; the result does not depend on it. */
+int lra_path_enhance_exec(lra_ctx* ctx, const void* R, int dtype, int64_t channels, int64_t h, int64_t w, const lra_enhance_tap* taps, const int32_t* starts, int n_filters, int mode,
+                          double cval, int clip, int rows, int cols, void* table, void* out);
+/* util.shear with the zero padding and the slice of the lag transforms folded in: `in` [rows_in][cols_in] and out [rows_out][cols_out] of
+ * esize-byte elements (1, 2, 4 or 8; device).  axis 1: out[r][c] = P[(r - factor c) mod period][c]; axis 0: out[r][c] = P[r][(c - factor r) mod
+ * period], where P is `in` followed by zeros up to `period` along the sheared axis. */
+int lra_shear_exec(lra_ctx* ctx, const void* in, int esize, int64_t rows_in, int64_t cols_in, int64_t period, int64_t rows_out, int64_t cols_out, int64_t factor, int axis, void* out);
+/* feature.stack_memory: in [batch][d][t] -> out [batch][n_steps d][t] of esize-byte elements (device), out[b][step d + i][j] = in[b][i][j - step
+ * delay] with np.pad's `mode` (LRA_STACK_*) applied to the column index; LRA_STACK_CONSTANT stores the low esize bytes of `fill`. */
+int lra_stack_memory_exec(lra_ctx* ctx, const void* in, int esize, int64_t batch, int64_t d, int64_t t, int64_t n_steps, int64_t delay, int mode, uint64_t fill, void* out);
+
 /* ---- the back half of pyin around the decode: librosa.pyin, librosa/core/pitch.py:796-852 and __pyin_helper :855-931 ---------------------- */
 #define LRA_PYIN_LDS_MAX (160 * 1024)
 /* Bytes of LDS a workgroup of lra_pyin_obs_exec needs (host arithmetic only): per frame the voiced row (8 n_pitch_bins) and two counters per

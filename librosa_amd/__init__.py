@@ -10,7 +10,8 @@ Only this path and the callers right next to it are provided -- ``magphase``, de
 ``phase_vocoder`` / ``effects.time_stretch``, ``decompose.hpss`` / ``effects.hpss``, ``pcen``, ``cqt`` / ``vqt``, ``stream``, ``resample``, ``onset.onset_strength`` / ``onset_strength_multi``,
 ``onset.onset_detect`` / ``onset_backtrack``, ``util.peak_pick``,
 ``feature.tempogram`` / ``fourier_tempogram`` / ``tempo``, ``beat.beat_track``, ``feature.chroma_stft`` / ``chroma_cqt`` (``tuning`` as a number), ``piptrack`` / ``pitch_tuning`` / ``estimate_tuning`` (which supplies that number on the device), ``yin``, ``pyin``,
-``sequence.viterbi`` / ``viterbi_discriminative`` / ``viterbi_binary`` with the ``sequence.transition_*`` builders, ``sequence.dtw`` / ``dtw_backtracking``, ``sequence.rqa``, ``segment.cross_similarity`` / ``recurrence_matrix``, and the frame / sample / time converters (see
+``sequence.viterbi`` / ``viterbi_discriminative`` / ``viterbi_binary`` with the ``sequence.transition_*`` builders, ``sequence.dtw`` / ``dtw_backtracking``, ``sequence.rqa``, ``segment.cross_similarity`` / ``recurrence_matrix``,
+``feature.stack_memory``, ``filters.diagonal_filter``, ``segment.path_enhance``, ``segment.recurrence_to_lag`` / ``lag_to_recurrence`` / ``timelag_filter``, ``util.shear``, and the frame / sample / time converters (see
 DESIGN.md for the scope table).  Host-side Python validates
 arguments exactly like the reference and builds the small float64 tables (window, mel basis, window
 sum-square); all signal arithmetic runs in hand-written HIP kernels through the C ABI declared in

@@ -107,6 +107,28 @@ class Session:
         self._keep.append(buf)
         return buf.ptr
 
+    # ---- elements moved as bytes (the gather kernels: any real or bool type, no value interpreted) ----
+    def input_bytes(self, x):
+        """A contiguous device copy of ``x`` as it is; returns (ptr, bytes per element)."""
+        if self.is_torch:
+            t = x.contiguous()
+            self._keep.append(t)
+            return t.data_ptr(), int(t.element_size())
+        a = np.ascontiguousarray(x)
+        buf = self.ctx.alloc(max(a.nbytes, 16)).upload(a)
+        self._keep.append(buf)
+        return buf.ptr, int(a.dtype.itemsize)
+
+    def output_like(self, shape, x):
+        """A device result of ``shape`` and of the type of ``x``; returns (ptr, handle) for ``result``."""
+        shape = tuple(int(s) for s in shape)
+        if self.is_torch:
+            t = _torch().empty(shape, dtype=x.dtype, device=self.device)
+            return t.data_ptr(), t
+        dtype = np.dtype(x.dtype)
+        ptr, (buf, _, _) = self.output((int(np.prod(shape, dtype=np.int64)) * dtype.itemsize,), np.uint8)
+        return ptr, (buf, shape, dtype)
+
     # ---- outputs --------------------------------------------------------------------------------
     def output(self, shape, dtype, rows=False):
         """Allocate a device result; returns (ptr, handle) where handle is finalised by ``result``.

@@ -142,6 +142,10 @@ SIGNATURES = {
     "lra_knn_emit_exec": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
     "lra_knn_dense_exec": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_int64, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lra_enhance_lds_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "lra_path_enhance_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "lra_shear_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),
+    "lra_stack_memory_exec": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.c_uint64, c_void_p]),
     "lra_tuning_work_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "lra_tuning_exec": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_double, c_void_p, c_double, c_double, c_int64,
                                 c_void_p, c_int64, c_double, c_void_p, c_void_p]),
@@ -787,6 +791,33 @@ class Context:
         """The transposed dense result where every candidate is kept (lra_knn_dense_exec)."""
         _check(self.lib.lra_knn_dense_exec(self.handle, c_void_p(q_ptr), c_void_p(r_ptr), dtype_code(dtype), int(n_features), int(n), int(m), int(metric), int(width), int(bool(self_link)),
                                            int(mode), int(bw_mode), float(bw_scalar), int(bool(bw_on_device)), c_void_p(sigma_ptr), c_void_p(matrix_ptr), c_void_p(work_ptr), c_void_p(out_ptr)))
+
+    ENHANCE_LDS_MAX, ENHANCE_MAX_REACH = 160 * 1024, 124   # LRA_ENHANCE_LDS_MAX, LRA_ENHANCE_MAX_REACH
+    ENHANCE_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}   # the LRA_ENHANCE_* boundary modes
+    STACK_MODES = {"constant": 0, "edge": 1, "reflect": 2, "symmetric": 3, "wrap": 4}     # the LRA_STACK_* pad modes
+    ENHANCE_TAP = np.dtype([("dr", "<i4"), ("dc", "<i4"), ("w", "<f8")])                  # lra_enhance_tap
+
+    @staticmethod
+    def enhance_table_bytes(n_taps, n_filters):
+        """LRA_ENHANCE_TABLE_BYTES."""
+        return ((int(n_filters) + 1) * 4 + 15) // 16 * 16 + 16 * int(n_taps)
+
+    def path_enhance_exec(self, r_ptr, dtype, channels, h, w, taps, starts, mode, cval, clip, rows, cols, table_ptr, out_ptr):
+        """All filters' responses, their maximum and the clip in one launch (``include/librosa_amd.h``: lra_path_enhance_exec).  ``taps``: a host
+        array of ``ENHANCE_TAP``; ``starts``: host int32, one more entry than filters."""
+        taps = np.ascontiguousarray(taps, dtype=self.ENHANCE_TAP)
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        _check(self.lib.lra_path_enhance_exec(self.handle, c_void_p(r_ptr), dtype_code(dtype), int(channels), int(h), int(w), c_void_p(taps.ctypes.data), c_void_p(starts.ctypes.data),
+                                              int(starts.size - 1), int(mode), float(cval), int(bool(clip)), int(rows), int(cols), c_void_p(table_ptr), c_void_p(out_ptr)))
+
+    def shear_exec(self, in_ptr, esize, rows_in, cols_in, period, rows_out, cols_out, factor, axis, out_ptr):
+        """The shear of a dense matrix with the lag transforms' pad and slice folded in (lra_shear_exec)."""
+        _check(self.lib.lra_shear_exec(self.handle, c_void_p(in_ptr), int(esize), int(rows_in), int(cols_in), int(period), int(rows_out), int(cols_out), int(factor), int(axis),
+                                       c_void_p(out_ptr)))
+
+    def stack_memory_exec(self, in_ptr, esize, batch, d, t, n_steps, delay, mode, fill, out_ptr):
+        """The delayed copies of [batch][d][t] stacked along d (lra_stack_memory_exec); ``fill``: the constant's bytes as an unsigned integer."""
+        _check(self.lib.lra_stack_memory_exec(self.handle, c_void_p(in_ptr), int(esize), int(batch), int(d), int(t), int(n_steps), int(delay), int(mode), int(fill), c_void_p(out_ptr)))
 
     VITERBI_GENERATIVE, VITERBI_DISCRIMINATIVE, VITERBI_BINARY, VITERBI_LOG = 0, 1, 2, 3   # the LRA_VITERBI_* kinds
     VITERBI_FLAG_NEGATIVE, VITERBI_FLAG_ABOVE_ONE, VITERBI_FLAG_COLUMN_SUM = 1, 2, 4       # the LRA_VITERBI_FLAG_* bits

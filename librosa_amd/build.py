@@ -5,7 +5,7 @@ one core, so the instances are split into groups (``csrc/lra_fused.h``) that are
 ``lra_inst.hip`` once per group plus the units of ``UNITS`` below -- ``lra_api.hip`` (host API of the transforms and everything without a unit
 of its own, general rocFFT path; it declares the fused kernels and compiles none of them) and one ``lra_<feature>_inst.hip`` per family of
 kernels, with the family's launchers and C entry points (mixed-radix transforms, tempogram, beat tracker, peak picker, chroma, pitch tracker
-and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA, neighbour graphs) -- then one link with ``-z defs``: a fused instance
+and tuning estimate, YIN, Viterbi, pYIN's observation stage, DTW, RQA, neighbour graphs, path enhancement with the lag and memory-stack gathers) -- then one link with ``-z defs``: a fused instance
 that the API unit launches and ``lra_fused.h`` does not list is an undefined symbol there, not at ``dlopen``.  The
 result ``librosa_amd/_liblibrosa_amd.so`` is git-ignored but travels to the GPU box with the repo snapshot.
 hipcc cross-compiles for gfx950 without a GPU.
@@ -27,7 +27,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # the translation units csrc/lra_<unit>.hip that are compiled once each (lra_inst.hip is compiled once per instance group besides);
 # scripts/device_asm_diff.sh reads this list
-UNITS = ("api", "mixed_inst", "rhythm_inst", "beat_inst", "peaks_inst", "chroma_inst", "pitch_inst", "yin_inst", "viterbi_inst", "pyin_inst", "dtw_inst", "rqa_inst", "knn_inst")
+UNITS = ("api", "mixed_inst", "rhythm_inst", "beat_inst", "peaks_inst", "chroma_inst", "pitch_inst", "yin_inst", "viterbi_inst", "pyin_inst", "dtw_inst", "rqa_inst", "knn_inst", "enhance_inst")
 
 
 def sources():

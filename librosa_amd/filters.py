@@ -17,7 +17,7 @@ from .core.convert import fft_frequencies, mel_frequencies
 from .util import utils as _u
 from .util.exceptions import ParameterError
 
-__all__ = ["get_window", "mel", "chroma", "cq_to_chroma", "window_sumsquare", "window_bandwidth", "wavelet", "wavelet_lengths"]
+__all__ = ["get_window", "mel", "chroma", "cq_to_chroma", "window_sumsquare", "window_bandwidth", "wavelet", "wavelet_lengths", "diagonal_filter"]
 
 
 def get_window(window, Nx, *, fftbins=True):
@@ -189,6 +189,37 @@ def cq_to_chroma_cached(n_input, *, bins_per_octave=12, n_chroma=12, fmin=None, 
         except TypeError:
             pass
     return cq_to_chroma(n_input, bins_per_octave=bins_per_octave, n_chroma=n_chroma, fmin=fmin, window=window, base_c=base_c, dtype=dtype)
+
+
+def diagonal_filter(window, n, *, slope=1.0, angle=None, zero_mean=False):
+    """Two-dimensional diagonal smoothing filter (``librosa/filters.py:1343-1408``), a float64 host table bit-identical to the reference's: the
+    window on the diagonal of an ``n x n`` matrix, rotated by ``scipy.ndimage.rotate(order=5, prefilter=False)`` to ``angle`` (``arctan(slope)``
+    where not given; the rotation grows the table), clipped at 0, normalised to sum 1, and with ``zero_mean`` shifted to mean 0."""
+    if angle is None:
+        angle = np.arctan(slope)
+    win = np.diag(get_window(window, n, fftbins=False))
+    if not np.isclose(angle, np.pi / 4):
+        import scipy.ndimage
+
+        win = scipy.ndimage.rotate(win, 45 - angle * 180 / np.pi, order=5, prefilter=False)
+    np.clip(win, 0, None, out=win)
+    win /= win.sum()
+    if zero_mean:
+        win -= win.mean()
+    return win
+
+
+@functools.lru_cache(maxsize=64)
+def _diagonal_filter_cached(window, n, slope, angle, zero_mean):
+    return _frozen(diagonal_filter(window, n, slope=slope, angle=angle, zero_mean=zero_mean))
+
+
+def diagonal_filter_cached(window, n, *, slope=1.0, angle=None, zero_mean=False):
+    """``diagonal_filter`` memoised on its (hashable) arguments; the array is then read-only."""
+    try:
+        return _diagonal_filter_cached(window, int(n), float(slope), None if angle is None else float(angle), bool(zero_mean))
+    except TypeError:  # unhashable window (an array or a list)
+        return diagonal_filter(window, n, slope=slope, angle=angle, zero_mean=zero_mean)
 
 
 # ---------------------------------------------------------------------------------------------------

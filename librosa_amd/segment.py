@@ -43,7 +43,8 @@ from . import _arrays
 from .util.exceptions import ParameterError
 from .util.utils import is_torch_tensor
 
-__all__ = ["cross_similarity", "recurrence_matrix"]
+__all__ = ["cross_similarity", "recurrence_matrix"]   # the neighbour graphs (pinned by tests/test_knn_host.py); the path-enhancement and time-lag functions
+ENHANCE_NAMES = ["path_enhance", "recurrence_to_lag", "lag_to_recurrence", "timelag_filter"]   # below are public attributes of this module as well
 
 KNN_ROWS = 0        # query frames per workgroup of the selection kernel: 0 for the library's choice, or a power of two up to 16
 KNN_TILE = 0        # candidate frames per tile: 0 for the library's choice, or a power of two from 4 to 1024 (rows * tile at most 2048)
@@ -289,3 +290,192 @@ def recurrence_matrix(data, *, k=None, width=1, metric="euclidean", sym=False, s
         k, width = t, 1   # (every other frame: the band is not cleared, the diagonal is)
     return _graph(data, data, q, q, t, t, k=k, bandwidth_k=bandwidth_k, width=width, metric=metric, sym=sym, sparse=sparse, mode=mode, bandwidth=bandwidth, self_link=self,
                   recurrence=True)
+
+
+# ---------------------------------------------------------------------------------------------------
+# path_enhance and the time-lag view: librosa/segment.py:1167-1329, :709-972
+# ---------------------------------------------------------------------------------------------------
+ENHANCE_ROWS = 0          # output rows per workgroup of the enhancement kernel: 0 (with ENHANCE_COLS 0) for the library's choice, or 1 .. 256
+ENHANCE_COLS = 0          # output columns per workgroup: 0, or 16, 32 or 64 (rows * cols at most 4096; tile plus halo must fit the LDS)
+ENHANCE_MAX_REACH = 124   # LRA_ENHANCE_MAX_REACH: the largest filter side is ENHANCE_MAX_REACH + 1 (the halo lives in LDS next to the tile)
+
+_ND_MODES = {"reflect": "reflect", "grid-mirror": "reflect", "constant": "constant", "grid-constant": "constant", "nearest": "nearest", "mirror": "mirror", "wrap": "wrap",
+             "grid-wrap": "wrap"}
+_ND_EPS = float(np.finfo(np.float64).eps)   # scipy.ndimage visits the weights with fabs(w) > DBL_EPSILON
+_INVALID_ORIGIN = "Invalid origin; origin must satisfy -(weights.shape[k] // 2) <= origin[k] <= (weights.shape[k]-1) // 2"
+
+
+def _filter_taps(kernels, origin=(0, 0)):
+    """The tap table of ``scipy.ndimage.convolve`` for a list of 2-D kernels: per kernel the weights of the flipped kernel that
+    ``scipy.ndimage`` visits (``fabs(w) > DBL_EPSILON``: exact zeros, rounding noise of the rotation and NaN are left out) in row-major order, each a row offset, a column offset and the weight (``_native.Context.ENHANCE_TAP``), and the kernels' ranges ``starts``.  With
+    ``Kf = K[::-1, ::-1]``, side ``m`` and ``o = -origin - (1 if m is even else 0)`` per axis, ``out[i, j]`` sums ``R[ext(i + a - m // 2 - o),
+    ext(j + b - m // 2 - o)] * Kf[a, b]`` over ``(a, b)``.  An origin outside SciPy's bounds raises ``ParameterError`` with SciPy's text."""
+    from ._native import Context
+
+    parts, starts = [], [0]
+    for K in kernels:
+        K = np.asarray(K, dtype=np.float64)
+        Kf = K[::-1, ::-1]
+        shift = []
+        for m, org in zip(K.shape, origin):
+            o = -int(org) - (0 if m & 1 else 1)
+            if o < -(m // 2) or o > (m - 1) // 2:
+                raise ParameterError(_INVALID_ORIGIN)
+            shift.append(m // 2 + o)
+        a, b = np.nonzero(np.abs(Kf) > _ND_EPS)   # (row-major; scipy.ndimage's footprint test, which also leaves a NaN weight out)
+        taps = np.empty(a.size, dtype=Context.ENHANCE_TAP)
+        taps["dr"], taps["dc"], taps["w"] = a - shift[0], b - shift[1], Kf[a, b]
+        parts.append(taps)
+        starts.append(starts[-1] + int(a.size))
+    return np.concatenate(parts), np.asarray(starts, dtype=np.int32)
+
+
+def _enhance_kwargs(kwargs, ndim):
+    """(mode, cval, (origin_row, origin_col)) of the keyword arguments ``scipy.ndimage.convolve`` takes here."""
+    for key in kwargs:
+        if key not in ("mode", "cval", "origin"):
+            raise ParameterError(f"path_enhance: the keyword argument {key!r} of scipy.ndimage.convolve is not served on the device (mode, cval and origin are)")
+    mode = kwargs.get("mode", "reflect")
+    if not isinstance(mode, str):
+        raise ParameterError(f"path_enhance: the keyword argument 'mode' must be one string for all axes, given {mode!r}")
+    if mode not in _ND_MODES:
+        raise ParameterError(f"path_enhance: mode={mode!r} is not a boundary mode of scipy.ndimage.convolve: one of {', '.join(_ND_MODES)}")
+    cval = float(kwargs.get("cval", 0.0))
+    origin = kwargs.get("origin", 0)
+    if np.ndim(origin) == 0:
+        origin = [int(origin)] * ndim
+    else:
+        origin = [int(o) for o in origin]
+        if len(origin) == 2 and ndim > 2:
+            origin = [0] * (ndim - 2) + origin   # (a pair: the matrix axes)
+        if len(origin) != ndim:
+            raise ParameterError(f"path_enhance: origin must be an integer or a pair, given {len(origin)} entries")
+    if any(origin[:-2]):   # (the kernel has side 1 along a channel axis)
+        raise ParameterError(_INVALID_ORIGIN)
+    return _ND_MODES[mode], cval, (origin[-2], origin[-1])
+
+
+def path_enhance(R, n, *, window="hann", max_ratio=2.0, min_ratio=None, n_filters=7, zero_mean=False, clip=True, **kwargs):
+    """Multi-angle path enhancement of a self- or cross-similarity matrix (``librosa/segment.py:1167-1329``): the element-wise maximum of ``R``
+    convolved with ``n_filters`` diagonal smoothing filters (``filters.diagonal_filter``) whose slopes run from ``min_ratio`` to ``max_ratio``,
+    clipped at 0 with ``clip``.  ``R`` is ``(..., h, w)``, float32 or float64; leading axes are independent channels.  One launch computes every
+    filter (``csrc/lra_enhance.h``); each response has the bits ``scipy.ndimage.convolve`` gives.  ``**kwargs``: ``mode``, ``cval`` and ``origin`` of
+    ``scipy.ndimage.convolve``.  NumPy in gives NumPy out, a device tensor gives a device tensor; the input is never written.
+
+    Differences from the reference: bool and integer ``R`` raise ``ParameterError`` (SciPy would truncate every response to the
+    input's type); so do complex or sparse ``R``, fewer than 2 dimensions, ``n_filters < 1``, any other keyword argument, and filters wider than
+    ``ENHANCE_MAX_REACH + 1`` cells."""
+    from . import filters
+
+    if min_ratio is None:
+        min_ratio = 1.0 / max_ratio
+    elif min_ratio > max_ratio:
+        raise ParameterError(f"min_ratio={min_ratio} cannot exceed max_ratio={max_ratio}")
+    if n_filters is None or int(n_filters) < 1:
+        raise ParameterError(f"n_filters={n_filters} must be a positive integer")
+    if not (is_torch_tensor(R) or isinstance(R, np.ndarray)):
+        if hasattr(R, "tocsr") or hasattr(R, "todense"):
+            raise ParameterError("path_enhance does not support sparse input: convert R to a dense array")
+        R = np.asarray(R)
+    if is_torch_tensor(R) and (R.is_sparse or R.layout != _arrays._torch().strided):
+        raise ParameterError("path_enhance does not support sparse input: convert R to a dense tensor")
+    if R.ndim < 2:
+        raise ParameterError(f"R must have at least 2 dimensions, given R.shape={tuple(R.shape)}")
+    if is_torch_tensor(R):
+        torch = _arrays._torch()
+        if R.is_complex():
+            raise ParameterError(f"R must be real-valued, given dtype={R.dtype}")
+        if R.dtype not in (torch.float32, torch.float64):
+            raise ParameterError(f"R must be float32 or float64, given dtype={R.dtype}: convert it (an integer matrix would truncate every filter response)")
+        real = np.dtype(np.float32 if R.dtype == torch.float32 else np.float64)
+    else:
+        if R.dtype.kind == "c":
+            raise ParameterError(f"R must be real-valued, given dtype={R.dtype}")
+        if R.dtype not in (np.float32, np.float64):
+            raise ParameterError(f"R must be float32 or float64, given dtype={R.dtype}: convert it (an integer matrix would truncate every filter response)")
+        real = R.dtype
+    mode, cval, origin = _enhance_kwargs(kwargs, R.ndim)
+    ratios = np.logspace(np.log2(min_ratio), np.log2(max_ratio), num=int(n_filters), base=2)
+    kernels = [filters.diagonal_filter_cached(window, n, slope=ratio, zero_mean=zero_mean) for ratio in ratios]
+    side = max(max(K.shape) for K in kernels)
+    if side - 1 > ENHANCE_MAX_REACH:
+        raise ParameterError(f"path_enhance: the widest of the filters spans {side} cells, above ENHANCE_MAX_REACH + 1 = {ENHANCE_MAX_REACH + 1}: its halo does not fit the LDS next to a tile")
+    taps, starts = _filter_taps(kernels, origin)
+    shape = tuple(int(s) for s in R.shape)
+    h, w = shape[-2:]
+    channels = int(np.prod(shape[:-2], dtype=np.int64))
+    if channels * h * w == 0:
+        raise ParameterError(f"R is empty: R.shape={shape}")
+    halo = (int(taps["dr"].max(initial=0) - taps["dr"].min(initial=0)), int(taps["dc"].max(initial=0) - taps["dc"].min(initial=0)))
+    sess = _arrays.Session(R)
+    try:
+        ctx = sess.ctx
+        if (ENHANCE_ROWS or ENHANCE_COLS) and not ctx.lib.lra_enhance_lds_bytes(int(ENHANCE_ROWS), int(ENHANCE_COLS), *halo):
+            raise ParameterError(f"ENHANCE_ROWS={ENHANCE_ROWS}, ENHANCE_COLS={ENHANCE_COLS}: rows 1 .. 256, cols 16, 32 or 64, rows * cols at most 4096, and the tile with its halo of "
+                                 f"{halo[0]} rows and {halo[1]} columns must fit ENHANCE_LDS_MAX={ctx.ENHANCE_LDS_MAX} bytes of LDS as float64")
+        r_ptr = sess.input_raw(R, real)
+        table = sess.scratch(ctx.enhance_table_bytes(taps.size, starts.size - 1))
+        out_ptr, out_h = sess.output(shape, real)
+        ctx.path_enhance_exec(r_ptr, real, channels, h, w, taps, starts, ctx.ENHANCE_MODES[mode], cval, clip, ENHANCE_ROWS, ENHANCE_COLS, table, out_ptr)
+        return sess.result(out_h)
+    finally:
+        sess.close()
+
+
+def recurrence_to_lag(rec, *, pad=True, axis=-1):
+    """Recurrence matrix to lag matrix, ``lag[i, j] == rec[i + j, j]`` (``librosa/segment.py:709-813``).  A dense matrix of any real or bool type,
+    NumPy or a device tensor, is moved by one gather launch, the zero padding of ``pad=True`` folded in; ``scipy.sparse`` input is handled on
+    the host as the reference does (index arithmetic only), its format kept."""
+    from .util.utils import _is_scipy_sparse, _shear_dense, shear
+
+    axis = int(np.abs(axis))
+    if rec.ndim != 2 or rec.shape[0] != rec.shape[1]:
+        raise ParameterError(f"non-square recurrence matrix shape: {tuple(rec.shape)}")
+    if _is_scipy_sparse(rec):
+        import scipy.sparse
+
+        fmt = rec.format
+        if pad:
+            padding = np.asarray([[1, 0]], dtype=rec.dtype).swapaxes(axis, 0)
+            rec = scipy.sparse.kron(padding, rec, format="csr" if axis == 0 else "csc")
+        return shear(rec, factor=-1, axis=axis).asformat(fmt)
+    t = int(rec.shape[axis])
+    out_shape = [t, t]
+    if pad:
+        out_shape[1 - axis] = 2 * t
+    return _shear_dense(rec, factor=-1, axis=axis, period=out_shape[1 - axis], out_shape=tuple(out_shape))
+
+
+def lag_to_recurrence(lag, *, axis=-1):
+    """Lag matrix to recurrence matrix (``librosa/segment.py:816-891``): the shear and the slice of the padded half in one gather launch for a
+    dense matrix; ``scipy.sparse`` input on the host as the reference does."""
+    from .util.utils import _is_scipy_sparse, _shear_dense, shear
+
+    if axis not in [0, 1, -1]:
+        raise ParameterError(f"Invalid target axis: {axis}")
+    axis = int(np.abs(axis))
+    if lag.ndim != 2 or (lag.shape[0] != lag.shape[1] and lag.shape[1 - axis] != 2 * lag.shape[axis]):
+        raise ParameterError(f"Invalid lag matrix shape: {tuple(lag.shape)}")
+    t = int(lag.shape[axis])
+    if _is_scipy_sparse(lag):
+        rec = shear(lag, factor=+1, axis=axis)
+        sub_slice = [slice(None)] * rec.ndim
+        sub_slice[1 - axis] = slice(t)
+        if rec.format == "coo":   # (not subscriptable: sliced in a compressed form, the format put back)
+            return rec.tocsc()[tuple(sub_slice)].asformat("coo")
+        return rec[tuple(sub_slice)]
+    return _shear_dense(lag, factor=+1, axis=axis, period=int(lag.shape[1 - axis]), out_shape=(t, t))
+
+
+def timelag_filter(function, pad=True, index=0):
+    """Wrap ``function`` so that it filters in the time-lag domain (``librosa/segment.py:895-972``): the argument at ``index`` goes through
+    ``recurrence_to_lag(pad=pad)``, the result through ``lag_to_recurrence``."""
+    import functools
+
+    @functools.wraps(function)
+    def wrapped(*args, **kwargs):
+        args = list(args)
+        args[index] = recurrence_to_lag(args[index], pad=pad)
+        return lag_to_recurrence(function(*args, **kwargs))
+
+    return wrapped

@@ -163,3 +163,79 @@ def sparsify_rows(x, *, quantile=0.01, dtype=None):
     share = np.cumsum(ascending / np.sum(magnitude, axis=1, keepdims=True), axis=1)
     cut = ascending[np.arange(x.shape[0]), np.argmin(share < quantile, axis=1)]          # per row: the smallest magnitude kept
     return scipy.sparse.csr_array((x * (magnitude >= cut[:, np.newaxis])).astype(out_dtype, copy=False))
+
+
+def _is_scipy_sparse(x) -> bool:
+    if is_torch_tensor(x) or isinstance(x, np.ndarray):
+        return False
+    import scipy.sparse
+
+    return scipy.sparse.issparse(x)
+
+
+def _refuse_torch_sparse(x, what):
+    if is_torch_tensor(x):
+        import torch
+
+        if x.layout != torch.strided:
+            raise ParameterError(f"{what} does not take a torch sparse tensor: pass a dense tensor or a scipy.sparse array")
+
+
+def _shear_dense(X, *, factor, axis, period, out_shape):
+    """One gather launch (``csrc/lra_enhance.h``: enhance_shear): ``out[r, c] = P[(r - factor c) mod period, c]`` for ``axis=1`` and the
+    transpose of that for ``axis=0``, where ``P`` is ``X`` followed by zeros up to ``period`` along the sheared axis and ``out_shape`` may stop
+    before the period.  Elements of 1, 2, 4 or 8 bytes are moved as they are."""
+    from .. import _arrays
+
+    _refuse_torch_sparse(X, "shear")
+    if not (is_torch_tensor(X) or isinstance(X, np.ndarray)):
+        X = np.asarray(X)
+    if X.ndim != 2:
+        raise ParameterError(f"Input must be 2D. Provided shape={tuple(X.shape)}.")
+    if (X.element_size() if is_torch_tensor(X) else X.dtype.itemsize) not in (1, 2, 4, 8):
+        raise ParameterError(f"shear moves elements of 1, 2, 4 or 8 bytes, given dtype={X.dtype}")
+    sess = _arrays.Session(X)
+    try:
+        ptr, esize = sess.input_bytes(X)
+        out_ptr, out_h = sess.output_like(out_shape, X)
+        if out_shape[0] and out_shape[1]:
+            sess.ctx.shear_exec(ptr, esize, X.shape[0], X.shape[1], period, out_shape[0], out_shape[1], factor, axis, out_ptr)
+        return sess.result(out_h)
+    finally:
+        sess.close()
+
+
+def _shear_sparse(X, *, factor, axis):
+    """``__shear_sparse`` (``librosa/util/utils.py:2158-2199``): index arithmetic on the CSC ``indices``; no data value is touched."""
+    import scipy.sparse
+
+    if X.ndim != 2:
+        raise ParameterError(f"Input must be 2D. Provided shape={X.shape}.")
+    fmt = X.format
+    is_matrix = isinstance(X, scipy.sparse.spmatrix)
+    make = scipy.sparse.csc_matrix if is_matrix else scipy.sparse.csc_array
+    X_in = X.T if axis == 0 else X
+    X_shear = make(X_in, copy=True)
+    roll = np.repeat(factor * np.arange(X_shear.shape[1]), np.diff(X_shear.indptr))
+    np.mod(X_shear.indices + roll, X_shear.shape[0], out=X_shear.indices)
+    if axis == 0:
+        X_shear = make(X_shear.T)
+    return X_shear.asformat(fmt)
+
+
+def shear(X, *, factor=1, axis=-1):
+    """Shear a matrix: column ``X[:, n]`` is rolled by ``factor * n`` (``librosa/util/utils.py:2206-2257``; ``axis=0`` rolls the rows).  A dense
+    matrix, NumPy or a device tensor, of any real or bool type is moved by one gather launch on the device; a ``scipy.sparse`` array or matrix is
+    sheared on the host through its indices, as the reference does, and keeps its format."""
+    if not np.issubdtype(type(factor), np.integer):
+        raise ParameterError(f"factor={factor} must be integer-valued")
+    if _is_scipy_sparse(X):
+        return _shear_sparse(X, factor=factor, axis=axis)
+    _refuse_torch_sparse(X, "shear")
+    if not (is_torch_tensor(X) or isinstance(X, np.ndarray)):
+        X = np.asarray(X)
+    if X.ndim != 2:
+        raise ParameterError(f"Input must be 2D. Provided shape={tuple(X.shape)}.")
+    axis = 0 if axis == 0 else 1   # (the reference's dense route shears the rows for axis == 0 and the columns for anything else)
+    shape = (int(X.shape[0]), int(X.shape[1]))
+    return _shear_dense(X, factor=int(factor), axis=axis, period=shape[1 - axis], out_shape=shape)
